@@ -11,8 +11,14 @@ RCCL all-reduce of gradients).
   python bench.py --config {2,3,4,5}    (BASELINE.json configs: per-GPU batch 64 | 64 x N ranks | frozen bert-base-uncased,
                                          batch 128 | MXFP8 forward, batch 256)
   python bench.py --gpus N --scaling strong   (global batch 256 = 256 / N per GPU; default weak: 256 per GPU)
+  python bench.py ... --dump-outputs DIR      (after the timed steps: what the last one computed, DIR/<name>.npy)
+  python bench.py ... --full                  (the measurements below besides the headline)
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").  `roofline` is the dominant kernel of the
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").  A plain run sets up, warms up, times the K steps and prints
+`value` / `ms_per_step` and the fields that need no further run.  `--full` adds what takes work of its own: the live
+kernel timing below (`roofline`, `roofline_ffn1`, `blocks`), the golden-batch `parity` with the precise mode and the fp16
+operand line, the f32-pixel / host->device / uint8 input loops, the other wire format, the other BASELINE configurations
+and `cpu_baseline` (the `--no-*` options leave parts of it out).  `roofline` is the dominant kernel of the
 step by GPU time (rocprofv3 --stats, profiles/): the weight-gradient instantiation of the bf16 MFMA ring
 GEMM, gemm256_kernel<1,1,EPI_F32_ATOMIC,4>, timed live with events on the launch stream around all of its
 launches (ViLT layers + patch projection) in every 4th timed step; `roofline_ffn1` is the same for the FFN-in forward GEMM (the
@@ -129,6 +135,32 @@ def resident_inputs(eng, spec, bn, dev):
     with_pixels = dict(rest, input_ids=stage["input_ids"], pixel_values=stage["pixel_values"],
                        pixel_mask=torch.from_numpy(bn["pixel_mask"]).to(dev))
     return with_patches, with_pixels, stage["labels"]
+
+
+DUMP_SAMPLE_PER_PARAM = 4096   # fp32 master-weight elements per parameter in params_sample.npy (seeded by the name)
+
+
+def dump_outputs(out_dir, stepper, spec, B, T):
+    """What the last timed step handed its caller, as float32 .npy files in `out_dir`: `loss` (the mean loss, [1]), `logits`
+    ([B, n_classes], the step's workspace) and `params_sample` - the fp32 master weights after the step's AdamW, per parameter
+    of the HF inventory in its order (vault_amd.spec.param_entries) all elements up to DUMP_SAMPLE_PER_PARAM, else that many drawn with
+    a generator seeded by the parameter's name (the same elements under any flat layout; 3.5 MB at the bench shape)."""
+    import zlib
+    from vault_amd.spec import param_entries
+    eng = stepper.engine
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize(eng.device)
+    np.save(os.path.join(out_dir, "loss.npy"), stepper.loss.detach().float().cpu().numpy().reshape(1))
+    np.save(os.path.join(out_dir, "logits.npy"), eng.workspace(B, T, True)["logits"].float().cpu().numpy())
+    parts = []
+    for name, _, _ in param_entries(spec):
+        w = eng.params.w(name).reshape(-1)
+        n = w.numel()
+        if n > DUMP_SAMPLE_PER_PARAM:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).integers(0, n, DUMP_SAMPLE_PER_PARAM))
+            w = w[torch.from_numpy(idx).to(w.device)]
+        parts.append(w.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "params_sample.npy"), np.concatenate(parts))
 
 
 def measure_parity(eng, spec, args, dev):
@@ -307,6 +339,11 @@ def main():
                          "`parity.fp16_operands`)")
     ap.add_argument("--no-parity", action="store_true", help="skip the golden-batch parity measurement and the precise-mode timing")
     ap.add_argument("--no-h2d", action="store_true", help="skip the second timed loop with pipelined host->device input copies")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: live kernel timing (roofline, blocks), parity, the other input forms, wire format "
+                         "and configurations, cpu_baseline (the --no-* options apply to this); off: the timed steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
     if args.config is not None:
         c = CONFIGS[args.config]
@@ -353,7 +390,7 @@ def main():
             raise SystemExit(f"--scaling strong: the global batch {args.batch} does not divide over {world} ranks")
         B = args.batch // world
     parity = None
-    if rank == 0 and not args.no_parity:
+    if args.full and rank == 0 and not args.no_parity:
         gname, par = measure_parity(eng, spec, args, dev)
         parity = {"golden": f"tests/golden/{gname}.npz (reference-generated, B = 2, eval mode)",
                   "mode": ("mxfp8 forward GEMMs" if args.fp8_forward else f"{args.half} MFMA operands, fp32 accumulate (the timed mode)"),
@@ -387,7 +424,7 @@ def main():
     step_ev = []          # one event pair per timed step on the launch stream: the median beside the mean
     t0 = time.perf_counter()
     for k in range(args.steps):
-        eng.profile_events = evs if (k % 4 == 0) else None
+        eng.profile_events = evs if (args.full and k % 4 == 0) else None
         e0 = torch.cuda.Event(enable_timing=True)
         e0.record()
         stepper(batch, labels)
@@ -400,6 +437,9 @@ def main():
     loss = float(stepper.loss.item())
     step_ms = sorted(a.elapsed_time(b) for a, b in step_ev)
     ms_median = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
+    if args.dump_outputs and rank == 0:
+        # (before the --full loops below step the same weights further)
+        dump_outputs(args.dump_outputs, stepper, spec, B, int(bn["input_ids"].shape[1]))
 
     ms_by_rank = [round(dt / args.steps * 1e3, 3)]
     if world > 1:
@@ -414,7 +454,7 @@ def main():
         exchange = {"wire": stepper.wire, "sparse_word_embedding": stepper.reducer.sparse is not None,
                     "bytes_sent_per_rank_and_step": int(stepper.reducer.wire_bytes),
                     "dense_f32_all_reduce_would_send": int(dense), "rccl_world_size": torch.distributed.get_world_size()}
-        if world > 1 or os.environ.get("VAULT_FORCE_DP") == "1":
+        if args.full and (world > 1 or os.environ.get("VAULT_FORCE_DP") == "1"):
             # the OTHER wire format on the same ranks, a short loop (the reducer reads its format at every launch: no
             # re-recording): informational - `value` above is the configured format's
             other = "bf16" if stepper.wire == "fp32" else "fp32"
@@ -437,7 +477,7 @@ def main():
     # ---- the same steps from f32 pixel_values resident in HBM (the reference's input tensor: the unfold pass - 0.68 GB of HBM
     #      traffic at batch 256 - runs inside the step); a short loop, informational
     f32pix = None
-    if not args.no_h2d:
+    if args.full and not args.no_h2d:
         n_p = max(4, args.steps // 2)
         for _ in range(2):
             stepper(batch_pix, labels)
@@ -460,7 +500,7 @@ def main():
     #      im2col - so the next batch travels under the rest of the current step; ids / masks / labels (read until the end of a
     #      step) go through two small device buffers and the engine's own restage
     h2d = None
-    if not args.no_h2d:
+    if args.full and not args.no_h2d:
         nb = 2
         host = []
         for i in range(nb):
@@ -522,7 +562,7 @@ def main():
     #      device batch - what HuggingFace's processor does per item on CPU workers in the reference
     #      (ref: vault/models/vault/dataset.py:337-341), bit-identically (tests/test_gpu_preprocess.py)
     u8 = None
-    if not args.no_h2d and not args.fp8_forward:
+    if args.full and not args.no_h2d and not args.fp8_forward:
         from vault_amd.preprocess import DeviceImageProcessor
         proc = DeviceImageProcessor(dev)
         HW = 480
@@ -578,7 +618,7 @@ def main():
                       "(no restage copy)"}
 
     precise_fwd = None
-    if rank == 0 and not args.no_parity and not args.fp8_forward:
+    if args.full and rank == 0 and not args.no_parity and not args.fp8_forward:
         # throughput of the mode that meets the north star's 1e-3: eval forward, split-bf16 GEMMs, at the bench batch
         ev = dict(batch_pix)       # (the split-bf16 mode splits f32 pixels: it takes pixel_values)
         for _ in range(2):
@@ -616,7 +656,7 @@ def main():
     # ---- the fp16 operand build beside the bf16 line (same box, same batch, same steps): TRAIN-mode logits / loss on the
     #      reference golden and the training throughput of that mode
     fp16_line = None
-    if rank == 0 and world == 1 and not args.no_parity and not args.fp8_forward and args.half == "bf16":
+    if args.full and rank == 0 and world == 1 and not args.no_parity and not args.fp8_forward and args.half == "bf16":
         try:
             fp16_line = measure_fp16(spec, args, dev, bn, B, steps=args.steps, warmup=args.warmup)
             # the bf16 steps once more, right behind the fp16 loop (same clock / thermal state of the box: the headline loop ran
@@ -636,8 +676,8 @@ def main():
     # ---- the other BASELINE configurations, each a short loop on its own engine (rank 0 prints them in `other_configs`):
     #      per-GPU batch 64 (config 2 on one GPU, config 3's per-GPU shape on N), and on one GPU the frozen-LM and fp8-forward ones
     others = None
-    if not args.no_other_configs and args.config is None and B == 256 and args.lm == "bertweet" and not args.freeze_lm \
-            and not args.fp8_forward:
+    if args.full and not args.no_other_configs and args.config is None and B == 256 and args.lm == "bertweet" \
+            and not args.freeze_lm and not args.fp8_forward:
         del stepper
         eng._ws.clear()
         torch.cuda.empty_cache()
@@ -696,20 +736,26 @@ def main():
                     "gflop_per_sample": round(fl / B / 1e9, 2), "achieved_tflops": round(fl / ((ms_f + ms_b) * 1e-3) / 1e12, 1),
                     "frac": round(fl / ((ms_f + ms_b) * 1e-3) / PEAK_BF16, 4), "steps_timed": len(tf)}
 
-        blk_vilt = block("vilt_fwd", "vilt_bwd", FLOP_VILT_BLOCK_FWD,
-                         f"12 ViLT layers (HF modeling_vilt.py:303-451), {M} token rows: LayerNorms, QKV / attention-out / FFN GEMMs, "
-                         "attention, their data gradients, attention / LayerNorm backward and the stack's weight-gradient launches")
-        blk_lm = block("lm_fwd", "lm_bwd", FLOP_LM_BLOCK_FWD,
-                       f"12 LM layers (HF modeling_roberta.py:222-398), {B * 40} token rows, "
-                       + ("forward only (frozen LM)" if args.freeze_lm else "forward + backward + weight gradients"))
-        r_wgrad = roof("wgrad", "gemm256_kernel<1,1,5,4,false,false> (static tile walk, no split-K form; A[K][M]^T B[K][N], EPI_F32_ATOMIC): the weight-gradient GEMMs, "
-                                f"dW[N x K] += dY[tokens][N]^T X[tokens][K] - grouped launches (vault_wgrad_grouped): the 256 x 256 tiles "
-                                f"of all four Linear kinds (FFN-out, FFN-in, attention-out, QKV) of a stack's layers packed into "
-                                f"rounds of 256 ({M} ViLT tokens / {B * 40} LM tokens per layer), and the patch projection",
-                       "r06_pmc_gemm_wgrad.json")
-        r_ffn1 = roof("ffn1", "gemm8w_kernel<7,4,true> / <1,4,true> (GELU epilogue with the 8-bit tile-native / bf16 gelu', 256-wide tiles, register-direct): FFN-in forward, ViLT "
-                              f"[{M}x{v.intermediate_size}x{v.hidden_size}] + LM [{B * 40}x{v.intermediate_size}x{v.hidden_size}]",
-                      "r06_pmc_gemm_ffn1.json")
+        live = {}           # (--full: the kernels and blocks timed live in every 4th step)
+        if args.full:
+            blk_vilt = block("vilt_fwd", "vilt_bwd", FLOP_VILT_BLOCK_FWD,
+                             f"12 ViLT layers (HF modeling_vilt.py:303-451), {M} token rows: LayerNorms, QKV / attention-out / FFN GEMMs, "
+                             "attention, their data gradients, attention / LayerNorm backward and the stack's weight-gradient launches")
+            blk_lm = block("lm_fwd", "lm_bwd", FLOP_LM_BLOCK_FWD,
+                           f"12 LM layers (HF modeling_roberta.py:222-398), {B * 40} token rows, "
+                           + ("forward only (frozen LM)" if args.freeze_lm else "forward + backward + weight gradients"))
+            r_wgrad = roof("wgrad", "gemm256_kernel<1,1,5,4,false,false> (static tile walk, no split-K form; A[K][M]^T B[K][N], EPI_F32_ATOMIC): the weight-gradient GEMMs, "
+                                    f"dW[N x K] += dY[tokens][N]^T X[tokens][K] - grouped launches (vault_wgrad_grouped): the 256 x 256 tiles "
+                                    f"of all four Linear kinds (FFN-out, FFN-in, attention-out, QKV) of a stack's layers packed into "
+                                    f"rounds of 256 ({M} ViLT tokens / {B * 40} LM tokens per layer), and the patch projection",
+                           "r06_pmc_gemm_wgrad.json")
+            r_ffn1 = roof("ffn1", "gemm8w_kernel<7,4,true> / <1,4,true> (GELU epilogue with the 8-bit tile-native / bf16 gelu', 256-wide tiles, register-direct): FFN-in forward, ViLT "
+                                  f"[{M}x{v.intermediate_size}x{v.hidden_size}] + LM [{B * 40}x{v.intermediate_size}x{v.hidden_size}]",
+                          "r06_pmc_gemm_ffn1.json")
+            live = {"roofline": r_wgrad, "roofline_ffn1": r_ffn1,
+                    "vilt_block_frac": None if blk_vilt is None else blk_vilt["frac"],
+                    "lm_block_frac": None if blk_lm is None else blk_lm["frac"],
+                    "blocks": {"vilt": blk_vilt, "lm": blk_lm}}
         out = {
             "metric": "train samples/sec (img+text pairs) ViLT-B32+BERTweet, bs256, 1/2/4/8 MI355X",
             "value": round(sps, 2), "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -719,7 +765,7 @@ def main():
             "vs_baseline": None, "dtype": "mxfp8 forward GEMMs / bf16 backward" if args.fp8_forward else args.half,
             "value_input_form": "since round 5 the image is resident as `pixel_patches` (the patch-embedding operand, what the input "
                                 "pipeline writes); rounds 1-4 timed f32 `pixel_values` with the unfold inside the step - that form is "
-                                "`with_f32_pixel_values` in this line (0.3 % apart)",
+                                "`with_f32_pixel_values` in the --full line (0.3 % apart)",
             "data": "synthetic",
             "config": {"workload": f"ViLT-B32 + {args.lm} fine-tune step (fwd+bwd+AdamW), per-GPU batch {B}, "
                                    f"40 text tokens + 384x384 image (185-token fused sequence; resident as the patch-embedding "
@@ -729,11 +775,8 @@ def main():
                        "global_batch": B * world, "seq_len": 185, "parallelism": f"dp{world}",
                        **({"baseline_config": args.config} if args.config is not None else {})},
             "ms_per_step_by_rank": ms_by_rank,
-            "roofline": r_wgrad, "roofline_ffn1": r_ffn1,
             "step_mfma_frac": round(sps / world * flop_per_sample / PEAK_BF16, 4),
-            "vilt_block_frac": None if blk_vilt is None else blk_vilt["frac"],
-            "lm_block_frac": None if blk_lm is None else blk_lm["frac"],
-            "blocks": {"vilt": blk_vilt, "lm": blk_lm},
+            **live,
             "final_loss": round(loss, 5),
         }
         if exchange is not None:
@@ -754,7 +797,7 @@ def main():
             out["with_h2d_input_copies"] = h2d
         if u8 is not None:
             out["with_uint8_input_pipeline"] = u8
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(spec)
             except Exception as e:  # pragma: no cover

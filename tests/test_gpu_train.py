@@ -611,7 +611,7 @@ def test_bench_refuses_two_ranks_on_the_one_gpu_box():
 
 
 def test_bench_line_carries_the_contract_fields_and_the_block_fractions():
-    """`python bench.py` as the driver runs it (a short loop at per-GPU batch 32 here): ONE JSON line on stdout with the
+    """`python bench.py --full` (a short loop here): ONE JSON line on stdout with the
     contract's fields, the `roofline` / `cpu_baseline`-shaped objects, and round 5's driver-visible north-star numbers -
     `vilt_block_frac` / `lm_block_frac` with the four block times behind them - consistent with each other; `--scaling strong`
     on one rank is the same workload labelled "strong"."""
@@ -619,7 +619,7 @@ def test_bench_line_carries_the_contract_fields_and_the_block_fractions():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--batch", "256", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--batch", "256", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline",
            "--no-other-configs", "--no-h2d", "--no-parity", "--scaling", "strong"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -641,6 +641,36 @@ def test_bench_line_carries_the_contract_fields_and_the_block_fractions():
     # the two stacks' blocks are most of the step, never more than it
     blocks_ms = bv["ms_forward"] + bv["ms_backward"] + bl["ms_forward"] + bl["ms_backward"]
     assert 0.85 * d["ms_per_step"] < blocks_ms < d["ms_per_step"]
+
+
+def test_plain_bench_line_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`python bench.py` without --full: the headline fields, the steps asked for, none of the --full measurements; with
+    --dump-outputs the loss / logits / sampled weights of the last timed step as float32 .npy files (64 MB at most)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--batch", "32", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "final_loss"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "samples/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) < 0.01 * d["value"]
+    for k in ("roofline", "blocks", "parity", "cpu_baseline", "other_configs", "with_f32_pixel_values", "with_h2d_input_copies",
+              "with_uint8_input_pipeline"):
+        assert k not in d, k
+    files = sorted(os.listdir(out))
+    assert files == ["logits.npy", "loss.npy", "params_sample.npy"], files
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 * 1024 * 1024
+    arrs = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert arrs["logits"].shape == (32, 3) and arrs["loss"].shape == (1,)
+    assert abs(float(arrs["loss"][0]) - d["final_loss"]) < 1e-4
 
 
 @pytest.mark.parametrize("wire,half", [("fp32", "bf16"), ("bf16", "bf16"), ("fp32", "fp16")])

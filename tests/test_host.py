@@ -637,6 +637,15 @@ def test_bench_refuses_more_ranks_than_devices():
     _bench_refusal()
 
 
+def test_bench_offers_full_and_dump_outputs():
+    """The plain line times the steps only; `--full` adds the other measurements, `--dump-outputs DIR` writes the last step's
+    outputs (tests/test_gpu_train.py runs both)."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-500:]
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
 def test_sysfs_device_count_honours_visibility_variables(monkeypatch):
     sys.path.insert(0, ROOT)
     import bench
