@@ -324,6 +324,28 @@ int vault_gelu_bwd(const float* x, const float* dy, float* dx, long long n, void
 int vault_adamw_step(float* p, float* g, float* m, float* v, void* p_bf16, long long n, float lr, float beta1,
                      float beta2, float eps, float weight_decay, float bias_corr_factor, float grad_scale,
                      int zero_grad, const unsigned char* zero_mask, void* stream);
+/* Global gradient-norm clipping (torch.nn.utils.clip_grad_norm_, HF TrainingArguments.max_grad_norm; the reference
+ * inherits the option but never applies it: ref vault/tmsc_utils/trainer.py:364-367).  Additions to ABI 12.
+ *   vault_grad_norm: out2[0] = sqrt(sum of g[0, n)^2) * |unscale| (f64 accumulation), out2[1] = min(1, max_norm /
+ *   (out2[0] + 1e-6)) in f32 as torch computes it (the reciprocal times max_norm; a NaN norm gives a NaN factor, an
+ *   infinite one 0).  unscale = the
+ *   optimizer's grad_scale (1 / (world x operand-format loss scale)).  Two launches, no atomics, nothing read back: a
+ *   fixed grid of at most VAULT_GRAD_NORM_PARTIALS blocks writes one f64 partial per block into `partials` (room for
+ *   VAULT_GRAD_NORM_PARTIALS doubles, caller-owned scratch), one block sums them in a fixed order - the same buffer gives the
+ *   same bits on every run and every rank.  n % 4 == 0, max_norm > 0 (+inf: the norm alone, factor 1).
+ *   vault_adamw_step_grouped: vault_adamw_step with parameter groups.  group_map: one byte per 64 elements of [0, n) (the
+ *   group of that range; every byte < n_groups, 1 <= n_groups <= 256); group_table: n_groups (lr, weight_decay) f32 pairs
+ *   in device memory; the step runs group k at lr = lr_factor x lr_k (lr_factor: the schedule multiplier, a host scalar).
+ *   coef (may be null = 1): the clip factor in device memory (vault_grad_norm out2 + 1); the gradient counts
+ *   g x grad_scale x coef.  Elements with g = m = v = 0 in a group without weight decay are skipped as in
+ *   vault_adamw_step, so p_bf16 must already mirror p there.  zero_grad / zero_mask as in vault_adamw_step.  With one
+ *   group, lr_factor = 1 and coef = 1 the result is bit-identical to vault_adamw_step. */
+#define VAULT_GRAD_NORM_PARTIALS 2048
+int vault_grad_norm(const float* g, long long n, double* partials, float* out2, float max_norm, float unscale, void* stream);
+int vault_adamw_step_grouped(float* p, float* g, float* m, float* v, void* p_bf16, long long n,
+                             const unsigned char* group_map, const float* group_table, int n_groups, float lr_factor,
+                             float beta1, float beta2, float eps, float bias_corr_factor, float grad_scale,
+                             const float* coef, int zero_grad, const unsigned char* zero_mask, void* stream);
 int vault_cast_bf16(const float* x, void* y_bf16, long long n, void* stream);
 /* Debug census of a 16-bit tensor in the library's operand format (ABI 9; nothing in the reference, which runs fp32:
  * ref vault/tmsc_utils/trainer.py:353-367 has no autocast): out4[0] += elements at the largest finite magnitude (what a

@@ -513,6 +513,34 @@ def adamw_step(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, bias_
             C.c_int(1 if zero_grad else 0), C.c_void_p(_p(zero_mask)), _stream())
 
 
+GRAD_NORM_PARTIALS = 2048     # f64 scratch elements grad_norm needs (include/vault_hip.h VAULT_GRAD_NORM_PARTIALS)
+
+
+def grad_norm(g, n, partials_f64, out2_f32, max_norm=float("inf"), unscale=1.0):
+    """out2[0] = ||g[0, n)|| x |unscale|, out2[1] = clip_grad_norm_'s factor min(1, max_norm / (norm + 1e-6)), both on the
+    device (vault_grad_norm: fixed-order reduction, the same bits on every run)."""
+    if partials_f64.dtype != torch.float64 or partials_f64.numel() < GRAD_NORM_PARTIALS or out2_f32.dtype != torch.float32 \
+            or out2_f32.numel() < 2:
+        raise ValueError(f"grad_norm needs {GRAD_NORM_PARTIALS} float64 partials and two float32 outputs")
+    _invoke("vault_grad_norm", C.c_void_p(_p(g)), C.c_longlong(n), C.c_void_p(_p(partials_f64)), C.c_void_p(_p(out2_f32)),
+            C.c_float(max_norm), C.c_float(unscale), _stream())
+
+
+def adamw_step_grouped(p, g, m, v, p_bf16, n, group_map, group_table, lr_factor, beta1, beta2, eps, bias_corr_factor=1.0,
+                       grad_scale=1.0, coef=None, zero_grad=True, zero_mask=None):
+    """AdamW with parameter groups (vault_adamw_step_grouped): ``group_map`` uint8, one group index per 64 elements of the
+    range; ``group_table`` f32 [n_groups, 2] of (lr, weight_decay) on the device; group k steps at lr_factor x lr_k;
+    ``coef``: optional device f32 scalar (the clip factor) multiplying the gradient."""
+    if group_map.dtype != torch.uint8 or group_table.dtype != torch.float32 or group_table.dim() != 2 \
+            or group_table.shape[1] != 2 or group_map.numel() < (n + 63) // 64:
+        raise ValueError("group_map: uint8, one byte per 64 elements; group_table: float32 [n_groups, 2]")
+    _invoke("vault_adamw_step_grouped", C.c_void_p(_p(p)), C.c_void_p(_p(g)), C.c_void_p(_p(m)), C.c_void_p(_p(v)),
+            C.c_void_p(_h(p_bf16)), C.c_longlong(n), C.c_void_p(_p(group_map)), C.c_void_p(_p(group_table)),
+            C.c_int(group_table.shape[0]), C.c_float(lr_factor), C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
+            C.c_float(bias_corr_factor), C.c_float(grad_scale), C.c_void_p(_p(coef)), C.c_int(1 if zero_grad else 0),
+            C.c_void_p(_p(zero_mask)), _stream())
+
+
 def cast_bf16(x, y_bf16, n):
     _invoke("vault_cast_bf16", C.c_void_p(_p(x)), C.c_void_p(_h(y_bf16)), C.c_longlong(n), _stream())
 

@@ -2,7 +2,7 @@
 HF ``state_dict`` names as views of them (ref: vault/models/vault/model.py:92-128 loads / saves by these names)."""
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -27,30 +27,24 @@ def _in_format(method):
     return run
 
 
+class ParamLayout(NamedTuple):
+    offsets: Dict[str, Tuple[int, Tuple[int, ...]]]     # name -> (element offset, shape); every offset 64-aligned
+    trainable: List[str]                               # in [0, n_train), flat order
+    frozen: List[str]                                  # behind n_train
+    n_train: int
+    n_total: int
+
+
 class ParamStore:
     def __init__(self, spec: VaultSpec, device, state: Optional[Dict[str, np.ndarray]] = None, seed: int = 0,
                  freeze_lm: bool = False, with_grads: bool = True, half: str = "bf16"):
         self.spec, self.device, self.freeze_lm = spec, device, freeze_lm
         self.half, self.hdt = half, ops.HALF_DTYPE[half]      # operand format of the shadow copies (bf16 | fp16)
-        entries = {n: s for n, s, _ in param_entries(spec)}
-        order = self._flat_order(spec)
-        assert set(order) == set(entries), "flat order must cover the parameter inventory"
-        no_grad = set(self.no_grad_names(spec, freeze_lm))
-        train = [n for n in order if n not in no_grad]
-        rest = [n for n in order if n in no_grad]
-        self.offsets: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
-        off = 0
-        for n in train:
-            self.offsets[n] = (off, entries[n])
-            off += _pad(int(np.prod(entries[n])), 64)
-        self.n_train = _pad(off, 1024)
-        off = self.n_train
-        for n in rest:
-            self.offsets[n] = (off, entries[n])
-            off += _pad(int(np.prod(entries[n])), 64)
-        self.n_total = _pad(off, 1024)
-        self.trainable = train
-        self.frozen = rest
+        lay = self.layout(spec, freeze_lm)
+        self.offsets: Dict[str, Tuple[int, Tuple[int, ...]]] = lay.offsets
+        self.n_train, self.n_total = lay.n_train, lay.n_total
+        self.trainable = lay.trainable
+        self.frozen = lay.frozen
         # the MLP head's output projection is used as a GEMM operand padded to a multiple of 256 rows: readable (zero)
         # slack behind the buffers, never part of [0, n_train) that the optimizer and the all-reduce walk
         self.slack = (256 * spec.mlp_dims[1] + 1024 if (spec.n_classes > 0 and spec.head == "mlp") else
@@ -73,6 +67,27 @@ class ParamStore:
             self.g = torch.zeros(self.n_train + self.slack, device=device)
             self.m = torch.zeros(self.n_train, device=device)
             self.v = torch.zeros(self.n_train, device=device)
+
+    @classmethod
+    def layout(cls, spec: VaultSpec, freeze_lm: bool = False) -> "ParamLayout":
+        """Where every parameter lives in the flat buffers (host only: nothing is allocated)."""
+        entries = {n: s for n, s, _ in param_entries(spec)}
+        order = cls._flat_order(spec)
+        assert set(order) == set(entries), "flat order must cover the parameter inventory"
+        no_grad = set(cls.no_grad_names(spec, freeze_lm))
+        train = [n for n in order if n not in no_grad]
+        rest = [n for n in order if n in no_grad]
+        offsets: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
+        off = 0
+        for n in train:
+            offsets[n] = (off, entries[n])
+            off += _pad(int(np.prod(entries[n])), 64)
+        n_train = _pad(off, 1024)
+        off = n_train
+        for n in rest:
+            offsets[n] = (off, entries[n])
+            off += _pad(int(np.prod(entries[n])), 64)
+        return ParamLayout(offsets, train, rest, n_train, _pad(off, 1024))
 
     @staticmethod
     def no_grad_names(spec: VaultSpec, freeze_lm: bool) -> List[str]:

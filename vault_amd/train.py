@@ -21,13 +21,15 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Optional, Tuple
+import re
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import ops
 from .engine import VaultEngine
+from .spec import VaultSpec, param_entries
 
 
 def linear_schedule(base_lr: float, step: int, warmup_steps: int, total_steps: int) -> float:
@@ -35,6 +37,76 @@ def linear_schedule(base_lr: float, step: int, warmup_steps: int, total_steps: i
     if step < warmup_steps:
         return base_lr * float(step) / float(max(1, warmup_steps))
     return base_lr * max(0.0, float(total_steps - step) / float(max(1, total_steps - warmup_steps)))
+
+
+# ---- parameter groups ------------------------------------------------------------------------------------------------
+# transformers' Trainer.get_decay_parameter_names: no weight decay on parameters whose lower-cased name matches one of these,
+# nor on any parameter of an nn.LayerNorm module
+NO_DECAY_PATTERNS = (r"bias", r"layernorm", r"rmsnorm", r"(?:^|\.)norm(?:$|\.)", r"_norm(?:$|\.)")
+MAX_PARAM_GROUPS = 256       # one byte per 64 elements in the group map (vault_adamw_step_grouped)
+
+
+def no_decay_parameter_names(spec: VaultSpec, names: Sequence[str]) -> List[str]:
+    """The names among ``names`` that an HF ``Trainer`` keeps out of weight decay: biases, every LayerNorm (BERT
+    ``LayerNorm``, ViLT ``layernorm_before`` / ``layernorm_after`` / the final ``layernorm``, the embedding LayerNorms - and the
+    MLP head's ``classifier.1``, a LayerNorm by module type, not by name)."""
+    ln_modules = {n for n, _, init in param_entries(spec) if init == "ln_w"}
+    pats = [re.compile(p_) for p_ in NO_DECAY_PATTERNS]
+    return [n for n in names if n in ln_modules or any(p_.search(n.lower()) for p_ in pats)]
+
+
+def hf_no_decay_groups(engine: VaultEngine) -> List[dict]:
+    """``param_groups`` for :class:`TrainStep` as an HF ``Trainer`` builds its optimizer: the no-decay parameters in one group
+    at weight decay 0, every other trainable parameter in the default group (the step's own ``weight_decay``)."""
+    return [{"params": no_decay_parameter_names(engine.spec, engine.params.trainable), "weight_decay": 0.0}]
+
+
+def build_param_groups(layout, param_groups: Optional[Sequence[dict]], lr: float, weight_decay: float):
+    """Check ``param_groups`` against a parameter layout (``offsets``, ``trainable``, ``n_train``: a ParamStore or
+    ParamStore.layout()) and return (group map: uint8 [n_train // 64], one group index per 64 elements; table: float32
+    [n_groups, 2] of base (lr, weight_decay)).  Group 0 is the default group - every trainable parameter no group names,
+    at (lr, weight_decay) - and group k + 1 is ``param_groups[k]``; its missing ``lr`` / ``weight_decay`` fall back to the
+    step's.  ValueError for a name that is unknown, not trainable or in two groups, and for any key but those three."""
+    groups = [] if param_groups is None else param_groups
+    if isinstance(groups, (dict, str)) or not isinstance(groups, Sequence):
+        raise ValueError("param_groups must be a sequence of dicts")
+    if len(groups) + 1 > MAX_PARAM_GROUPS:
+        raise ValueError(f"at most {MAX_PARAM_GROUPS - 1} parameter groups (besides the default group)")
+    trainable = set(layout.trainable)
+    table = [(float(lr), float(weight_decay))]
+    gmap = np.zeros(layout.n_train // 64, np.uint8)
+    owner: Dict[str, int] = {}
+    for k, grp in enumerate(groups):
+        if not isinstance(grp, dict):
+            raise ValueError(f"param_groups[{k}] is not a dict")
+        extra = set(grp) - {"params", "lr", "weight_decay"}
+        if extra:
+            raise ValueError(f"param_groups[{k}]: unsupported key(s) {sorted(extra)} (only params, lr and weight_decay "
+                             "are per group; betas and eps are the step's)")
+        names = grp.get("params")
+        if names is None or isinstance(names, str):
+            raise ValueError(f"param_groups[{k}]['params'] must be a list of parameter names")
+        vals = []
+        for key, default in (("lr", lr), ("weight_decay", weight_decay)):
+            try:
+                val = float(grp.get(key, default))
+            except (TypeError, ValueError):
+                raise ValueError(f"param_groups[{k}]['{key}'] is not a number") from None
+            if not math.isfinite(val):
+                raise ValueError(f"param_groups[{k}]['{key}'] is not finite")
+            vals.append(val)
+        table.append(tuple(vals))
+        for n in names:
+            if n not in layout.offsets:
+                raise ValueError(f"param_groups[{k}]: unknown parameter {n!r}")
+            if n not in trainable:
+                raise ValueError(f"param_groups[{k}]: {n!r} is not trained by this engine (frozen or without gradient)")
+            if n in owner:
+                raise ValueError(f"{n!r} is in param_groups[{owner[n]}] and param_groups[{k}]")
+            owner[n] = k
+            o, shp = layout.offsets[n]
+            gmap[o // 64:(o + int(np.prod(shp)) + 63) // 64] = k + 1      # (every tensor starts 64-aligned)
+    return gmap, np.asarray(table, np.float32).reshape(-1, 2)
 
 
 class GradBuckets:
@@ -434,9 +506,29 @@ class TrainStep:
                  correct_bias: bool = False, warmup_ratio: float = 0.1, total_steps: int = 1000,
                  process_group=None, bucket_mb: float = 64.0, constant_lr: bool = False, use_tape: bool = True,
                  assume_full_pixel_mask: bool = False, wire: Optional[str] = None, sparse_embedding: Optional[bool] = None,
-                 precise_forward: bool = False):
+                 precise_forward: bool = False, max_grad_norm: Optional[float] = None,
+                 param_groups: Optional[Sequence[dict]] = None, track_grad_norm: bool = False):
+        """``max_grad_norm``: clip the global L2 norm of the gradient before AdamW (torch.nn.utils.clip_grad_norm_, HF
+        ``TrainingArguments.max_grad_norm``); ``param_groups``: ``[{"params": [names], "lr": .., "weight_decay": ..}, ..]``
+        (engine parameter names = state_dict keys; unnamed parameters form the default group at ``learning_rate`` /
+        ``weight_decay``; every group follows the schedule from its own base lr); ``track_grad_norm``: keep the norm without
+        clipping.  With either norm option ``grad_norm`` holds the step's pre-clip norm on the device."""
         self.engine = engine
         self.lr, self.b1, self.b2, self.eps, self.wd = learning_rate, adam_beta1, adam_beta2, adam_epsilon, weight_decay
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0.0):
+            raise ValueError("max_grad_norm must be positive (None: no clipping)")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.track_grad_norm = bool(track_grad_norm)
+        # the step's gradient norm (0-dim f32 on the device, written by the kernel: no host sync), None without the options
+        self.grad_norm: Optional[torch.Tensor] = None
+        self._group_map = self._group_table = self._norm_partials = None
+        if param_groups is not None or self.max_grad_norm is not None:
+            # the grouped AdamW (one group when only clipping is asked for: it reads the clip factor from the device)
+            gmap, table = build_param_groups(engine.params, param_groups, learning_rate, weight_decay)
+            self._group_map = torch.from_numpy(gmap).to(engine.device)
+            self._group_table = torch.from_numpy(table).to(engine.device)
+        if self._needs_norm:
+            self._norm_partials = torch.empty(ops.GRAD_NORM_PARTIALS, dtype=torch.float64, device=engine.device)
         self.correct_bias = correct_bias
         self.total_steps = int(total_steps)
         self.warmup_steps = int(warmup_ratio * self.total_steps)
@@ -495,10 +587,20 @@ class TrainStep:
                                          process_group, torch.cuda.Stream(device=engine.device), engine.device,
                                          wire=self.wire, sparse=sparse)
 
+    @property
+    def _needs_norm(self) -> bool:
+        return self.max_grad_norm is not None or self.track_grad_norm
+
     def current_lr(self) -> float:
         if self.constant_lr:
             return self.lr
         return linear_schedule(self.lr, self.step_idx, self.warmup_steps, self.total_steps)
+
+    def lr_factor(self) -> float:
+        """The schedule's multiplier of every group's base lr at the current step (LambdaLR)."""
+        if self.constant_lr:
+            return 1.0
+        return linear_schedule(1.0, self.step_idx, self.warmup_steps, self.total_steps)
 
     def __call__(self, batch: Dict[str, torch.Tensor], labels: torch.Tensor) -> torch.Tensor:
         """One optimisation step.  The first call for a (B, T) shape runs eagerly and records the call
@@ -558,7 +660,11 @@ class TrainStep:
                                        "(patch-embedding GEMM, its weight gradient)")
                 self._tape, self._tape_key, self._tape_ws, self._loss_buf = tape, key, ws, out["loss"]
                 self._zero_mask = self._build_zero_mask(eng._stored_ranges)
-            if self.reducer:
+            if self.reducer and self._needs_norm:
+                # the gradient norm needs the whole reduced gradient: no optimizer pass under the last bucket's exchange
+                self.reducer.finish()
+                self.optimizer_step(zero_mask=self._zero_mask)
+            elif self.reducer:
                 # optimizer on the already reduced upper part of the flat buffer while the last bucket (LM / ViLT
                 # embeddings: the lowest addresses) is still being all-reduced, then on the rest
                 x = self.reducer.finish_upper()
@@ -598,10 +704,18 @@ class TrainStep:
         """Fused HF-AdamW over elements [lo, hi) of the flat parameter buffer (default: all trainable ones);
         ``advance=False`` leaves the step counter alone (first part of a split update).  ``zero_mask`` (one byte per 64
         elements of the WHOLE buffer, 0 = leave the gradient un-zeroed) is the fused step's own: a caller that steps the
-        optimizer by hand (gradient accumulation, a manual loop) gets every gradient it read cleared."""
+        optimizer by hand (gradient accumulation, a manual loop) gets every gradient it read cleared.
+        With ``max_grad_norm`` / ``track_grad_norm`` a pass over the whole range first measures the gradient norm (and
+        clips); clipping refuses a partial range.  With parameter groups ``lo`` must be 64-aligned."""
         eng = self.engine
         P = eng.params
         hi = P.n_train if hi is None else hi
+        full = lo == 0 and hi == P.n_train
+        if hi > lo and not full and self.max_grad_norm is not None:
+            raise ValueError("max_grad_norm: the optimizer step must cover every trainable element (the norm needs the "
+                             "whole gradient)")
+        if hi > lo and self._group_map is not None and lo % 64:
+            raise ValueError("parameter groups: the optimizer range must start at a multiple of 64 elements")
         t = self.step_idx + 1
         bc = 1.0
         if self.correct_bias:
@@ -610,13 +724,27 @@ class TrainStep:
             if hi > lo:
                 # (the gradients carry the operand format's power-of-two scale - fp16: engine.grad_scale - and the sum
                 #  over the ranks: both are divided out here)
+                gscale = 1.0 / (self.world * eng.grad_scale)
                 zm = zero_mask
                 if zm is not None and (lo % 64 or (hi - lo) % 64):
                     zm = None          # (never for the engine's 64-aligned stage boundaries)
-                ops.adamw_step(P.p[lo:hi], P.g[lo:hi], P.m[lo:hi], P.v[lo:hi], P.pb[lo:hi], hi - lo, self.current_lr(),
-                               self.b1, self.b2, self.eps, self.wd, bias_corr_factor=bc,
-                               grad_scale=1.0 / (self.world * eng.grad_scale), zero_grad=True,
-                               zero_mask=None if zm is None else zm[lo // 64:hi // 64])
+                coef = None
+                if full and self._needs_norm:
+                    # norm of the reduced, unscaled gradient and the clip factor, both left on the device for AdamW
+                    out = torch.empty(2, dtype=torch.float32, device=eng.device)
+                    ops.grad_norm(P.g, P.n_train, self._norm_partials, out,
+                                  self.max_grad_norm if self.max_grad_norm is not None else math.inf, gscale)
+                    self.grad_norm = out[0]
+                    coef = out[1:] if self.max_grad_norm is not None else None
+                if self._group_map is not None:
+                    ops.adamw_step_grouped(P.p[lo:hi], P.g[lo:hi], P.m[lo:hi], P.v[lo:hi], P.pb[lo:hi], hi - lo,
+                                           self._group_map[lo // 64:(hi + 63) // 64], self._group_table, self.lr_factor(),
+                                           self.b1, self.b2, self.eps, bias_corr_factor=bc, grad_scale=gscale, coef=coef,
+                                           zero_grad=True, zero_mask=None if zm is None else zm[lo // 64:hi // 64])
+                else:
+                    ops.adamw_step(P.p[lo:hi], P.g[lo:hi], P.m[lo:hi], P.v[lo:hi], P.pb[lo:hi], hi - lo, self.current_lr(),
+                                   self.b1, self.b2, self.eps, self.wd, bias_corr_factor=bc, grad_scale=gscale,
+                                   zero_grad=True, zero_mask=None if zm is None else zm[lo // 64:hi // 64])
         if advance:
             with torch.cuda.device(eng.device):
                 P.refresh_transposed()   # W^T shadow of the data-gradient GEMMs, from the bf16 shadow just written
