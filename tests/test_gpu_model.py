@@ -445,6 +445,39 @@ def test_batched_weight_gradients_equal_the_per_layer_ones(group):
     assert float((grads[0] - grads[1]).norm() / grads[0].norm()) < 1e-5   # float-atomic summation order only
 
 
+@pytest.mark.parametrize("batched", [True, False])
+def test_per_kernel_layer_path_equals_the_stage_calls(batched):
+    """The per-kernel layer sequences of the engine (STAGE_MAX_ROWS = 0) and the stage-level C calls (csrc/stage.hip) run the
+    same kernels in the same order: same stage tags, and loss, logits and gradients equal up to the summation order of float
+    atomics.  B = 5 leaves padded rows in every GEMM; the two layers of a tiny stack give a group boundary (groups of one layer in
+    the batched case), the bias gradient handed to the layer below and the embedding backward ahead of the last group;
+    dropout stays on: the per-layer stream numbers of both paths."""
+    spec = VaultSpec.tiny(3, "roberta")
+    state = build_state(spec, 0)
+    b = _dev(synthetic_batch(spec, 5, seed=31, n_classes=3))
+    res = []
+    for stage in (True, False):
+        eng = VaultEngine(spec, "cuda:0", state=state, seed=0, classifier_dropout=0.0, half="bf16")
+        if not stage:
+            eng.STAGE_MAX_ROWS = 0
+        eng.LM_WGRAD_BATCHED = batched
+        if batched:
+            eng.dp_world, eng.LM_WGRAD_GROUP = 2, 1
+        out = eng.forward(b, train=True, labels=b["labels"], need_hidden=False)
+        eng.zero_grad()
+        seen = []
+        eng.backward(after_layer=seen.append)
+        torch.cuda.synchronize()
+        assert eng.last["vilt_stage"] is stage and eng.last["lm_stage"] is stage
+        res.append((seen, out["loss"].clone().view(-1), out["logits"].clone().view(-1),
+                    eng.params.g[: eng.params.n_train].clone()))
+    assert res[0][0] == res[1][0], (res[0][0], res[1][0])
+    for name, a, c in zip(("loss", "logits", "gradient"), res[0][1:], res[1][1:]):
+        rel = float((a - c).norm() / a.norm())
+        print(f"{name}: relative L2 {rel:.3e}")
+        assert rel < 1e-5, (name, rel)       # float-atomic summation order only
+
+
 def test_full_size_against_reference_golden():
     """12+12 layers, hidden 768, B=2 (one padded caption): compare with numbers produced by the
     reference (HuggingFace ViltModel + RobertaModel under ref VaultForTMSC) in the build container."""

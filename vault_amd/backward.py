@@ -3,6 +3,7 @@ vault/tmsc_utils/trainer.py:365): the chain of data gradients layer by layer, to
 gradients of a stack packed into full rounds of 256 x 256 tiles."""
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional
 
 import torch
@@ -77,6 +78,15 @@ class BackwardMixin:
         if bname is not None:
             ops.colsum(dy_bf16, Nout, m_valid, Nout, P.gr(bname, n_elems=Nout, shape=(Nout,)))
 
+    @staticmethod
+    def _wgrad_splits(items, per_round, nk, fixed, fixed_unsplit=None):
+        """Split count (1 .. 8, two 64-token k-steps each at least) of a persistent weight-gradient launch by a cost model: rounds of
+        ``per_round`` blocks over ``items`` tiles x (k-steps at 1.67 us + ``fixed`` us per item; ``fixed_unsplit``: un-split, may store)."""
+        def cost(sp):
+            fx = fixed_unsplit if (sp == 1 and fixed_unsplit is not None) else fixed
+            return -(-items * sp // per_round) * (1.67 * -(-nk // sp) + fx)
+        return min((sp for sp in range(1, 9) if nk // sp >= 2), key=cost)
+
     def _wgrad_batched(self, dY_all, X_all, wnames, i0, Mtok_pad, Nout, Kin, m_valid):
         """dW_l[Nout,Kin] += dY_l[Mtok,Nout]^T . X_l[Mtok,Kin] for the consecutive layers l = i0 .. i0 + len(wnames) - 1 of a
         stack in ONE launch (vault_gemm `batch`): dY_l / X_l are slices of the stacked operand tensors, the dW_l lie
@@ -91,10 +101,9 @@ class BackwardMixin:
         nk = Mtok_pad // 64
         if Nout % 256 == 0 and Kin % 256 == 0:
             # ring kernel, persistent over (layer, split, tile) items, layer-major: an XCD works on whole layers.  Split
-            # count by a cost model of the launch: rounds of 256 blocks x (k-steps at 1.67 us + ~40 us fixed per item)
+            # count by the cost model of the launch (~40 us fixed per item)
             cfg, tiles = 3, (Nout // 256) * (Kin // 256) * G
-            cost = lambda sp: -(-tiles * sp // 256) * (1.67 * -(-nk // sp) + 40.0)   # noqa: E731
-            splits = min((sp for sp in range(1, 9) if nk // sp >= 2), key=cost)
+            splits = self._wgrad_splits(tiles, 256, nk, 40.0)
         else:
             cfg, tiles = 0, (Nout // 128) * (Kin // 128) * G
             splits = max(1, min(8, Mtok_pad // 512, int(round(512.0 / tiles))))   # ~two resident 128x128 blocks per CU
@@ -176,10 +185,8 @@ class BackwardMixin:
             count = sum(c for _, _, c in segs)
             if count == CU:
                 splits = 1
-            else:       # remainder: rounds of 256 pieces x (k-steps at 1.67 us + fixed cost per piece: ~10 us stored, ~50 us with float atomics)
-                fixed = lambda sp: 10.0 if (sp == 1 and self._grads_zero) else 50.0   # noqa: E731
-                cost = lambda sp: -(-count * sp // CU) * (1.67 * -(-nk // sp) + fixed(sp))   # noqa: E731
-                splits = min((sp for sp in range(1, 9) if nk // sp >= 2), key=cost)
+            else:       # remainder: fixed cost per piece ~10 us stored, ~50 us with float atomics
+                splits = self._wgrad_splits(count, CU, nk, 50.0, 10.0 if self._grads_zero else 50.0)
             acc = 0 if (self._grads_zero and splits == 1) else 1
             args = []
             for k, first, c in segs:
@@ -255,24 +262,20 @@ class BackwardMixin:
             self.zero_grad()
         self._g_dirty = True
 
+    @contextlib.contextmanager
     def _grads_scaled(self):
         """Context for a backward outside the fused train step when the operand format carries a gradient scale (fp16): the
         flat gradient buffer may hold earlier, un-scaled contributions (gradient accumulation, several encoder passes): it
         is multiplied by the scale before and by its inverse after the backward - exact, a power of two."""
-        eng = self
-
-        class _Ctx:
-            def __enter__(self_c):
-                if eng.grad_scale != 1.0 and eng.params.g is not None:
-                    with ops.operand_format(eng.half):
-                        ops.scale(eng.params.g, eng.grad_scale, eng.params.n_train)
-
-            def __exit__(self_c, *exc):
-                if eng.grad_scale != 1.0 and eng.params.g is not None:
-                    with ops.operand_format(eng.half):
-                        ops.scale(eng.params.g, 1.0 / eng.grad_scale, eng.params.n_train)
-                return False
-        return _Ctx()
+        def rescale(factor):
+            if self.grad_scale != 1.0 and self.params.g is not None:
+                with ops.operand_format(self.half):
+                    ops.scale(self.params.g, factor, self.params.n_train)
+        rescale(self.grad_scale)
+        try:
+            yield
+        finally:
+            rescale(1.0 / self.grad_scale)
 
     def _scaled_in(self, ws, name, t):
         """An externally supplied output gradient (f32) times the gradient scale, in a workspace buffer (identity at 1)."""
@@ -295,39 +298,62 @@ class BackwardMixin:
         ws = self.last if ws is None else ws
         if ws is None or not ws.get("train"):
             raise RuntimeError("backward() needs a preceding forward(train=True)")
-        spec, P = self.spec, self.params
-        v = spec.vilt
-        B, T, S, M, Mp, H, FF, heads, NP = (ws[k] for k in ("B", "T", "S", "M", "Mp", "H", "FF", "heads", "NP"))
-        Ml, Mlp = ws["Ml"], ws["Mlp"]
-        bf = self.hdt
-        buf = lambda name, shape, dtype=torch.float32: self._buf(ws, name, shape, dtype)  # noqa: E731
         self.drop_seed = ws["drop_seed"]
-        x = ws["x"]
-        nv = v.num_hidden_layers
-        if after_layer is not None:
-            note = lambda tag: ops.pycall(lambda: after_layer(tag))  # noqa: E731
-        else:
-            note = lambda tag: None  # noqa: E731
-
+        note = (lambda tag: ops.pycall(lambda: after_layer(tag))) if after_layer is not None else (lambda tag: None)
         # deferred weight gradients beside the backward chain when its GEMMs are single partial rounds of tiles (same-box
         # A/B: B = 8 9.76 -> 9.48 ms/step, B = 64 16.12 -> 15.69; B = 256 43.5 -> 43.2: within noise, and concurrent
         # kernels would blur the per-kernel timings the roofline line is built on - serial there)
-        self._wgrad_side = Mp <= self.WGRAD_STREAM_MAX_ROWS
-        dx = [buf("dx_a", (Mp, H))]          # f32 gradient at the bottom of the ViLT stack (the embedding backward reads it)
-        dxb = [buf("dxb_a", (Mp, H), bf), buf("dxb_b", (Mp, H), bf)]
-        vbatch = self.LM_WGRAD_BATCHED and "act_all" in ws and P.gr(self.vl[0].fw) is not None
-        if vbatch:
-            # dY operands of every ViLT layer stay alive until their group's batched weight-gradient launches:
-            # A = gradient at the layer output (FFN-out's dY), B = gradient behind the attention block (attn-out's dY)
-            dxbA_all = self._stack(ws, "v_dxbA", nv, (Mp, H), bf); dxbB_all = self._stack(ws, "v_dxbB", nv, (Mp, H), bf)
-            dU_all = self._stack(ws, "v_dU", nv, (Mp, FF), bf); dqkv_all = self._stack(ws, "v_dqkv", nv, (Mp, 3 * H), bf)
-            vgroup = self._wgrad_group_size(nv, after_layer, "vilt")
-        dxb_top = dxbA_all[nv - 1] if vbatch else dxb[0]
+        self._wgrad_side = ws["Mp"] <= self.WGRAD_STREAM_MAX_ROWS
+        vb = self._vilt_grad_buffers(ws, after_layer)
+        self._backward_head(ws, vb["top"], grad_scale, dlogits, dpooled, dhidden)
+        note("head")
+        self._backward_vilt_stack(ws, vb, after_layer, note)
+        dvs = self._backward_vilt_embeddings(ws, vb["dx"], after_layer)
+        note("vilt_embed")
+        if self.spec.lm is None or self.freeze_lm:
+            self._join_wgrads()
+        else:
+            self._backward_lm_stack(ws, dvs, after_layer, note)
+        self._run_census(ws, "backward")
+
+    # ---- deferred weight gradients of a stack: groups of layers ------------------------------------
+    def _wgrad_groups(self, ws, tag, layers, after_layer, dY, X, rows_pad, rows):
+        """A stack's deferred weight gradients (_layer_done): ``dY`` stacks of FFN-out, FFN-in, attention-out, QKV; ``X``: names of theirs."""
+        H, FF = ws["H"], ws["FF"]
+        kinds = tuple((dy, ws[x], wsel, no, ki) for dy, x, (wsel, no, ki) in
+                      zip(dY, X, (("fw", H, FF), ("iw", FF, H), ("ow", H, H), ("qw", 3 * H, H))))
+        return dict(layers=layers, size=self._wgrad_group_size(len(layers), after_layer, tag), kinds=kinds, H=H,
+                    rows_pad=rows_pad, rows=rows)
+
+    def _layer_done(self, tag, grp, i, note, after_layer, N=None, hm=0, parts=None, items=0, ahead=None):
+        """Layer ``i`` of a stack has run its data gradients: report it (per-layer weight gradients: ``grp`` None) or, at the bottom
+        layer of a group, launch the group's QKV bias sums (the first ``N`` columns of dqkv, default all 3H; ``hm`` / ``parts``:
+        head-major dqkv / the attention backward's partial sums) and weight gradients - ``ahead()`` first, ``items``:
+        _wgrads_aside - and report the group's layers top down."""
+        if grp is None:
+            note(f"{tag}{i}")
+        if grp is None or i % grp["size"]:
+            return
+        layers, kinds, H, hi = grp["layers"], grp["kinds"], grp["H"], min(len(grp["layers"]), i + grp["size"])
+        if ahead is not None:
+            ahead()
+
+        def launch():
+            self._qkv_bias_grads_batched(kinds[3][0], layers, i, hi, 3 * H, grp["rows"], 3 * H if N is None else N, hm=hm, parts=parts)
+            self._wgrad_group(kinds[:3] + (kinds[3] + (hm,),), layers, i, hi, grp["rows_pad"], grp["rows"])
+        self._wgrads_aside(launch, after_layer, items=items)
+        for j in reversed(range(i, hi)):
+            note(f"{tag}{j}")
+
+    # ---- head / tail ------------------------------------------------------------------------------
+    def _backward_head(self, ws, dxb_top, grad_scale, dlogits, dpooled, dhidden):
+        """Classifier / pooler / final LayerNorm: the gradient at the top of the ViLT stack into ``dxb_top``."""
+        spec, P, x, nv = self.spec, self.params, ws["x"], len(self.vl)
+        B, S, M, H = (ws[k] for k in ("B", "S", "M", "H"))
         ops.pycall(dxb_top.zero_)
-        # ------------------------------ tail ------------------------------
         if spec.add_pooling_layer and (spec.n_classes > 0 or dpooled is not None):
             Bp = ws["Bp"]
-            dpre = buf("dpre", (Bp, H), bf)
+            dpre = self._buf(ws, "dpre", (Bp, H), self.hdt)
             if spec.n_classes > 0 and spec.head == "mlp" and dpooled is None:
                 if dlogits is None:
                     raise ValueError("the MLP head has no built-in loss: pass dlogits (the autograd bridge does)")
@@ -343,7 +369,7 @@ class BackwardMixin:
             else:
                 ops.tanh_bwd(ws["pooled"], self._scaled_in(ws, "dpooled_scaled", dpooled), dpre, B * H)
             self._wgrad(dpre, ws["h0b"], "pooler.dense.weight", "pooler.dense.bias", Bp, H, H, B)
-            dh0 = buf("dh0", (Bp, H), bf)
+            dh0 = self._buf(ws, "dh0", (Bp, H), self.hdt)
             self._dgrad(dpre, "pooler.dense.weight", dh0, Bp, H, H, ops.EPI_BF16, B)
             ops.layernorm_bwd(x[nv], ws["f_mean"], ws["f_rstd"], P.w("layernorm.weight"), B, H, dy_bf16=dh0,
                               dx_bf16=dxb_top, dgamma=P.gr("layernorm.weight"),
@@ -357,112 +383,118 @@ class BackwardMixin:
                               dx_bf16=dxb_top,
                               dgamma=P.gr("layernorm.weight"), dbeta=P.gr("layernorm.bias"),
                               dbias=P.gr(self.vl[nv - 1].fb))
-        note("head")
 
-        # ------------------------------ ViLT encoder ------------------------------
-        dN = buf("dN", (Mp, H), bf); dctx = buf("dctx", (Mp, H), bf)
-        if not vbatch:
-            dU = buf("dU", (Mp, FF), bf); dqkv = buf("dqkv", (Mp, 3 * H), bf)
+    # ---- encoder layers through the stage-level C ABI ----------------------------------------------
+    def _layer_bwd_staged(self, ws, style, layers, i, d, deferred):
+        """One C call (csrc/stage.hip: the kernels of _vilt_layer_bwd / _lm_layer_bwd in their order); ``d``: vault_layer_bwd_args members."""
+        P, ln, H = self.params, layers[i], ws["H"]
+        a = ws[f"stage_{style}{i}"]
+        if style == "lm":
+            a.drop_seed = self.drop_seed & 0xFFFFFFFF
+        gb = ops.layer_bwd_args(
+            a, **d, do_wgrad=0 if deferred else 1, g_wqkv=P.gr(ln.qw, n_elems=3 * H * H, shape=(3 * H, H)),
+            g_bqkv=None if deferred else P.gr(ln.qb, n_elems=3 * H, shape=(3 * H,)),      # (deferred: with the group's launches)
+            g_wo=P.gr(ln.ow), g_bo=P.gr(ln.ob), g_wi=P.gr(ln.iw), g_bi=P.gr(ln.ib), g_wf=P.gr(ln.fw),
+            g_ln1w=P.gr(ln.ln1w), g_ln1b=P.gr(ln.ln1b), g_ln2w=P.gr(ln.ln2w), g_ln2b=P.gr(ln.ln2b),
+            # (the FFN-out bias gradient: post-LN LM - this layer's, from its LN2 backward; pre-LN ViLT - the layer's below)
+            g_bf=P.gr(ln.fb) if style == "lm" else None,
+            g_bf_below=P.gr(layers[i - 1].fb) if (style == "vilt" and i > 0) else None)
+        ws[f"stage_{style}_bwd{i}"] = gb
+        ops.layer_call(f"vault_{style}_layer_bwd", gb, seeded=bool(a.attn_drop_thresh or a.hid_drop_thresh))
+
+    # ---- ViLT stack -------------------------------------------------------------------------------
+    def _vilt_grad_buffers(self, ws, after_layer):
+        """``dx`` (f32 gradient at the bottom of the stack: the embedding backward reads it), the two 16-bit buffers of the residual-
+        gradient stream or - deferred weight gradients - the per-layer ``dY`` stacks with their groups ``grp``, ``top``: the head's."""
+        Mp, H, FF, nv, bf = ws["Mp"], ws["H"], ws["FF"], len(self.vl), self.hdt
+        vb = dict(dx=self._buf(ws, "dx_a", (Mp, H), torch.float32), grp=None,
+                  dxb=(self._buf(ws, "dxb_a", (Mp, H), bf), self._buf(ws, "dxb_b", (Mp, H), bf)))
+        if self.LM_WGRAD_BATCHED and "act_all" in ws and self.params.gr(self.vl[0].fw) is not None:
+            # dY operands of every ViLT layer stay alive until their group's batched weight-gradient launches:
+            # A = gradient at the layer output (FFN-out's dY), B = gradient behind the attention block (attn-out's dY)
+            vb["dY"] = (self._stack(ws, "v_dxbA", nv, (Mp, H), bf), self._stack(ws, "v_dU", nv, (Mp, FF), bf),
+                        self._stack(ws, "v_dxbB", nv, (Mp, H), bf), self._stack(ws, "v_dqkv", nv, (Mp, 3 * H), bf))
+            vb["grp"] = self._wgrad_groups(ws, "vilt", self.vl, after_layer, vb["dY"],
+                                           ("act_all", "n2_all", "ctx_all", "n1_all"), Mp, ws["M"])
+        vb["top"] = vb["dY"][0][nv - 1] if vb["grp"] else vb["dxb"][0]
+        return vb
+
+    def _backward_vilt_stack(self, ws, vb, after_layer, note):
+        """The pre-LN ViLT layers, top down.  Residual-gradient stream in bf16 only (GRAD_STREAM_BF16): a layer's incoming
+        gradient is ONE bf16 tensor - stream and FFN-out dY at once -, the LayerNorm backward adds it as `dres_bf16` and writes
+        only the bf16 result (10 instead of 16 B per element); the bottom layer also writes f32 for the embedding backward."""
+        B, S, Mp, H, FF, heads, nv, bf = ws["B"], ws["S"], ws["Mp"], ws["H"], ws["FF"], ws["heads"], len(self.vl), self.hdt
+        grp, staged, (dxa, dxb) = vb["grp"], bool(ws.get("vilt_stage")), vb["dxb"]
+        d = dict(dN=self._buf(ws, "dN", (Mp, H), bf), dctx=self._buf(ws, "dctx", (Mp, H), bf))
+        if not grp:
+            d.update(dy_bf16=dxa, dmid_bf16=dxb, dx_bf16=dxa, dU=self._buf(ws, "dU", (Mp, FF), bf), dqkv=self._buf(ws, "dqkv", (Mp, 3 * H), bf))
         # QKV bias gradient from inside the attention backward (vault_attn_args.bias_partials) where the deferred launches would
-        # otherwise re-read dqkv for it: the query third (the shortcut below covers key / value: no attention dropout here)
-        vparts, vthirds = None, 1
-        if vbatch and self.QKV_BIAS_SHORTCUT and not ws.get("vilt_stage"):
-            npart = ops.attention_bwd_partials(B, S, H, heads, vthirds)
+        # otherwise re-read dqkv for it: the query third (the shortcut covers key / value: no attention dropout here).  The
+        # stage call takes neither: the group's launches sum all of (row-major) dqkv
+        short, vparts = bool(grp) and self.QKV_BIAS_SHORTCUT and not staged, None
+        if short:
+            npart = ops.attention_bwd_partials(B, S, H, heads, 1)
             if npart:
-                vparts = (self._stack(ws, "v_qbpart", nv, (npart, vthirds * H), torch.float32), npart)
-        km = ws["keymask"]
-        cur = 0
-        # Residual-gradient stream of the pre-LN ViLT stack in bf16 only (GRAD_STREAM_BF16): a layer's incoming gradient is ONE
-        # bf16 tensor - stream and FFN-out dY at once -, the LayerNorm backward adds it as `dres_bf16` and writes only the bf16
-        # result (10 instead of 16 B per element); the bottom layer also writes f32 for the embedding backward.
+                vparts = (self._stack(ws, "v_qbpart", nv, (npart, H), torch.float32), npart)
+        # the whole stack's group, launched when the ViLT chain is through, with a trained LM stack's backward next: that
+        # chain's GEMMs are partial rounds of tiles at any batch (40 row panels at B = 256) - the group runs beside it
+        beside = self.WGRAD_BESIDE_LM_ITEMS if (grp and grp["size"] >= nv and not staged and self.spec.lm is not None
+                                                and not self.freeze_lm and not self._wgrad_side) else 0
         ops.pycall(lambda: self._prof_begin("vilt_bwd"))
         for i in reversed(range(nv)):
-            ln = self.vl[i]
-            g = lambda k: ws[f"{k}{i}"]  # noqa: E731
-            if vbatch:
-                dyA, dyB, dU, dqkv = dxbA_all[i], dxbB_all[i], dU_all[i], dqkv_all[i]
-                dyN = dxbA_all[i - 1] if i > 0 else dxb[0]
+            if grp:
+                d["dy_bf16"], d["dU"], d["dmid_bf16"], d["dqkv"] = (t[i] for t in vb["dY"])
+                d["dx_bf16"] = vb["dY"][0][i - 1] if i > 0 else dxa
+            d["dx_f32"] = vb["dx"] if i == 0 else None
+            if staged:
+                self._layer_bwd_staged(ws, "vilt", self.vl, i, d, bool(grp))
             else:
-                dyA, dyB, dyN = dxb[cur], dxb[cur ^ 1], dxb[cur]
-            if ws.get("vilt_stage"):
-                # the whole layer backward in one C call (csrc/stage.hip: the same kernels in the same order as below)
-                gb = ops.layer_bwd_args(
-                    ws[f"stage_vilt{i}"], dy_bf16=dyA, dx_f32=dx[cur] if i == 0 else None, dx_bf16=dyN, dU=dU, dN=dN,
-                    dctx=dctx, dqkv=dqkv, dmid_bf16=dyB, do_wgrad=0 if vbatch else 1,
-                    g_wqkv=P.gr(ln.qw, n_elems=3 * H * H, shape=(3 * H, H)),
-                    g_bqkv=None if vbatch else P.gr(ln.qb, n_elems=3 * H, shape=(3 * H,)),      # (batched: with the group's launches)
-                    g_wo=P.gr(ln.ow), g_bo=P.gr(ln.ob), g_wi=P.gr(ln.iw), g_bi=P.gr(ln.ib), g_wf=P.gr(ln.fw),
-                    g_ln1w=P.gr(ln.ln1w), g_ln1b=P.gr(ln.ln1b), g_ln2w=P.gr(ln.ln2w), g_ln2b=P.gr(ln.ln2b),
-                    g_bf_below=P.gr(self.vl[i - 1].fb) if i > 0 else None)
-                ws[f"stage_vilt_bwd{i}"] = gb
-                ops.layer_call("vault_vilt_layer_bwd", gb)
-                if not vbatch:
-                    note(f"vilt{i}")
-                elif i % vgroup == 0:
-                    hi = min(nv, i + vgroup)
-                    def launch(i=i, hi=hi):
-                        self._qkv_bias_grads_batched(dqkv_all, self.vl, i, hi, 3 * H, M, 3 * H)
-                        self._wgrad_group(((dxbA_all, ws["act_all"], "fw", H, FF), (dU_all, ws["n2_all"], "iw", FF, H),
-                                           (dxbB_all, ws["ctx_all"], "ow", H, H), (dqkv_all, ws["n1_all"], "qw", 3 * H, H)),
-                                          self.vl, i, hi, Mp, M)
-                    self._wgrads_aside(launch, after_layer)
-                    for j in reversed(range(i, hi)):
-                        note(f"vilt{j}")
-                continue
-            # FFN
-            # (bias gradients are column sums of dY: fused into the kernel that PRODUCES dY - the LayerNorm
-            #  backward for the residual-stream gradient, the GEMM epilogue for dU)
-            g8 = ws.get("gelu8_active")
-            g8kw = dict(cfg=g8, aux_u8=True) if g8 is not None else {}
-            self._dgrad(dyA, ln.fw, dU, Mp, FF, H, ops.EPI_BF16_DGELU, M, aux=g("u"), colsum=P.gr(ln.ib), **g8kw)
-            if not vbatch:
-                self._wgrad(dyA, g("act"), ln.fw, None, Mp, H, FF, M)
-            self._dgrad(dU, ln.iw, dN, Mp, H, FF, ops.EPI_BF16, M)
-            if not vbatch:
-                self._wgrad(dU, g("n2"), ln.iw, None, Mp, FF, H, M)
-            ops.layernorm_bwd(g("xm"), g("m2"), g("r2"), P.w(ln.ln2w), M, H, dy_bf16=dN, dres_bf16=dyA, dx_bf16=dyB,
-                              dgamma=P.gr(ln.ln2w), dbeta=P.gr(ln.ln2b), dbias=P.gr(ln.ob))
-            # attention
-            # QKV bias gradient without a pass over all of dqkv (QKV_BIAS_SHORTCUT; the ViLT stack has no attention dropout,
-            # D2): softmax rows sum to one, so  sum_keys dV = sum_queries dO  - the value bias gradient is the column sum of
-            # dctx, taken in the epilogue of the GEMM that produces dctx; sum_keys dS = 0 for every query, so the key bias
-            # gradient is zero (the reference's autograd leaves rounding noise of 1e-9 there); only the query third is summed
-            short = vbatch and self.QKV_BIAS_SHORTCUT
-            gqb = P.gr(ln.qb, n_elems=3 * H, shape=(3 * H,))
-            self._dgrad(dyB, ln.ow, dctx, Mp, H, H, ops.EPI_BF16, M, **(dict(colsum=gqb[2 * H:]) if short else {}))
-            if not vbatch:
-                self._wgrad(dyB, g("ctx"), ln.ow, None, Mp, H, H, M)
-            vhm = ws.get("qkv_hm", 0)
-            ops.attention_bwd(g("qkv"), km, g("ctx"), g("lse"), dctx, dqkv, B, S, H, heads, qkv_hm=vhm,
-                              **(dict(bias_partials=vparts[0][i], bias_thirds=vthirds) if vparts else {}))
-            self._dgrad(dqkv, ln.qw, dN, Mp, H, 3 * H, ops.EPI_BF16, M, **(dict(a_hm=vhm) if vhm else {}))
-            if not vbatch:
-                self._wgrad(dqkv, g("n1"), ln.qw, ln.qb, Mp, 3 * H, H, M)
-            # (vbatch: the query third - or, without the shortcut, all of it - with the group's batched launches below)
-            ops.layernorm_bwd(x[i], g("m1"), g("r1"), P.w(ln.ln1w), M, H, dy_bf16=dN, dres_bf16=dyB,
-                              dx_f32=dx[cur] if i == 0 else None, dx_bf16=dyN, dgamma=P.gr(ln.ln1w), dbeta=P.gr(ln.ln1b),
-                              dbias=P.gr(self.vl[i - 1].fb) if i > 0 else None)
-            if not vbatch:
-                note(f"vilt{i}")
-            elif i % vgroup == 0:
-                hi = min(nv, i + vgroup)
-                def launch(i=i, hi=hi, short=short, vhm=vhm):
-                    self._qkv_bias_grads_batched(dqkv_all, self.vl, i, hi, 3 * H, M, H if short else 3 * H, hm=vhm, parts=vparts)
-                    self._wgrad_group(((dxbA_all, ws["act_all"], "fw", H, FF), (dU_all, ws["n2_all"], "iw", FF, H),
-                                       (dxbB_all, ws["ctx_all"], "ow", H, H), (dqkv_all, ws["n1_all"], "qw", 3 * H, H, vhm)),
-                                      self.vl, i, hi, Mp, M)
-                # the whole stack's group, launched when the ViLT chain is through, with a trained LM stack's backward next: that
-                # chain's GEMMs are partial rounds of tiles at any batch (40 row panels at B = 256) - the group runs beside it
-                beside = self.WGRAD_BESIDE_LM_ITEMS if (i == 0 and hi == nv and spec.lm is not None and not self.freeze_lm and not self._wgrad_side) else 0
-                self._wgrads_aside(launch, after_layer, items=beside)
-                for j in reversed(range(i, hi)):
-                    note(f"vilt{j}")
-
+                self._vilt_layer_bwd(ws, i, d, bool(grp), short, vparts)
+            self._layer_done("vilt", grp, i, note, after_layer, H if short else 3 * H, ws.get("qkv_hm", 0), vparts, beside)
         ops.pycall(lambda: self._prof_end("vilt_bwd"))
-        # ------------------------------ ViLT embeddings ------------------------------
-        dx0 = dx[cur]
-        Kp, Mpp = ws["Kp"], ws["Mpp"]
-        dyp = buf("dyp", (Mpp, H), bf)
+
+    def _vilt_layer_bwd(self, ws, i, d, deferred, short, vparts):
+        """The layer backward kernel by kernel (``deferred``: without its weight gradients)."""
+        P, ln, vhm = self.params, self.vl[i], ws.get("qkv_hm", 0)
+        B, S, M, Mp, H, FF, heads = (ws[k] for k in ("B", "S", "M", "Mp", "H", "FF", "heads"))
+        g = lambda k: ws[f"{k}{i}"]  # noqa: E731
+        wgrad = (lambda *a: None) if deferred else self._wgrad      # (deferred: with the group's launches, _layer_done)
+        dyA, dyB, dU, dqkv, dN, dctx = (d[k] for k in ("dy_bf16", "dmid_bf16", "dU", "dqkv", "dN", "dctx"))
+        # FFN
+        # (bias gradients are column sums of dY: fused into the kernel that PRODUCES dY - the LayerNorm
+        #  backward for the residual-stream gradient, the GEMM epilogue for dU)
+        g8 = ws.get("gelu8_active")
+        g8kw = dict(cfg=g8, aux_u8=True) if g8 is not None else {}
+        self._dgrad(dyA, ln.fw, dU, Mp, FF, H, ops.EPI_BF16_DGELU, M, aux=g("u"), colsum=P.gr(ln.ib), **g8kw)
+        wgrad(dyA, g("act"), ln.fw, None, Mp, H, FF, M)
+        self._dgrad(dU, ln.iw, dN, Mp, H, FF, ops.EPI_BF16, M)
+        wgrad(dU, g("n2"), ln.iw, None, Mp, FF, H, M)
+        ops.layernorm_bwd(g("xm"), g("m2"), g("r2"), P.w(ln.ln2w), M, H, dy_bf16=dN, dres_bf16=dyA, dx_bf16=dyB,
+                          dgamma=P.gr(ln.ln2w), dbeta=P.gr(ln.ln2b), dbias=P.gr(ln.ob))
+        # attention
+        # QKV bias gradient without a pass over all of dqkv (``short``: QKV_BIAS_SHORTCUT; the ViLT stack has no attention
+        # dropout, D2): softmax rows sum to one, so  sum_keys dV = sum_queries dO  - the value bias gradient is the column sum of
+        # dctx, taken in the epilogue of the GEMM that produces dctx; sum_keys dS = 0 for every query, so the key bias
+        # gradient is zero (the reference's autograd leaves rounding noise of 1e-9 there); only the query third is summed
+        gqb = P.gr(ln.qb, n_elems=3 * H, shape=(3 * H,))
+        self._dgrad(dyB, ln.ow, dctx, Mp, H, H, ops.EPI_BF16, M, **(dict(colsum=gqb[2 * H:]) if short else {}))
+        wgrad(dyB, g("ctx"), ln.ow, None, Mp, H, H, M)
+        ops.attention_bwd(g("qkv"), ws["keymask"], g("ctx"), g("lse"), dctx, dqkv, B, S, H, heads, qkv_hm=vhm,
+                          **(dict(bias_partials=vparts[0][i], bias_thirds=1) if vparts else {}))
+        self._dgrad(dqkv, ln.qw, dN, Mp, H, 3 * H, ops.EPI_BF16, M, **(dict(a_hm=vhm) if vhm else {}))
+        wgrad(dqkv, g("n1"), ln.qw, ln.qb, Mp, 3 * H, H, M)
+        # (deferred: the QKV bias gradient's query third - or, without the shortcut, all of it - with the group's launches)
+        ops.layernorm_bwd(ws["x"][i], g("m1"), g("r1"), P.w(ln.ln1w), M, H, dy_bf16=dN, dres_bf16=dyB,
+                          dx_f32=d["dx_f32"], dx_bf16=d["dx_bf16"], dgamma=P.gr(ln.ln1w), dbeta=P.gr(ln.ln1b),
+                          dbias=P.gr(self.vl[i - 1].fb) if i > 0 else None)
+
+    # ---- ViLT embeddings --------------------------------------------------------------------------
+    def _backward_vilt_embeddings(self, ws, dx0, after_layer):
+        """Image rows (patch projection with its weight gradient) and text rows; returns the f32 gradient of the text embedding sum."""
+        spec, P, v = self.spec, self.params, self.spec.vilt
+        B, T, S, H, NP, Ml, Mlp, Kp, Mpp = (ws[k] for k in ("B", "T", "S", "H", "NP", "Ml", "Mlp", "Kp", "Mpp"))
+        buf = lambda name, shape, dtype=torch.float32: self._buf(ws, name, shape, dtype)  # noqa: E731
+        dyp = buf("dyp", (Mpp, H), self.hdt)
         gpos = P.gr("embeddings.position_embeddings", shape=(v.num_patches + 1, H))
         gmt = P.gr("embeddings.token_type_embeddings.weight")
         if ws.get("img_embeds") is not None:
@@ -502,140 +534,104 @@ class BackwardMixin:
         if ws["use_pos"]:
             gt.append((P.gr("embeddings.text_embeddings.position_embeddings.weight"), "mod"))
         ops.scatter_add(dvs, gt, Ml, H, period=T)
-        note("vilt_embed")
-        if spec.lm is None or self.freeze_lm:
-            self._join_wgrads()
-            self._run_census(ws, "backward")
-            return
+        return dvs
 
-        # ------------------------------ language model ------------------------------
-        lm = spec.lm
-        nl = lm.num_hidden_layers
-        y, yb = ws["lm_y"], ws["lm_yb"]
-        amf = ws["amf"]
-        pdh, pda = lm.hidden_dropout_prob, lm.attention_probs_dropout_prob
-        dh = buf("lm_dh", (Mlp, H)); dh1 = buf("lm_dh1", (Mlp, H))
-        batched = self.LM_WGRAD_BATCHED and "lm_act_all" in ws and P.gr(self.ll[0].fw) is not None
-        if batched:
+    # ---- language model ---------------------------------------------------------------------------
+    def _backward_lm_stack(self, ws, dvs, after_layer, note):
+        """The post-LN LM layers, top down, from ``dvs`` (f32 gradient of the stack's output), then its embeddings."""
+        B, T, H, FF, heads, Ml, Mlp = (ws[k] for k in ("B", "T", "H", "FF", "heads", "Ml", "Mlp"))
+        nl, bf, staged = len(self.ll), self.hdt, bool(ws.get("lm_stage"))
+        buf = lambda name, shape, dtype=torch.float32: self._buf(ws, name, shape, dtype)  # noqa: E731
+        # gradient at a layer's output: bf16 part (the QKV data gradient of the layer above, left in dN) + f32 part (its dx_f32):
+        # consumed by the layer's LN2 backward before either is overwritten
+        dN, grp = buf("lm_dN", (Mlp, H), bf), None
+        d = dict(dy_bf16=None, dy_f32=dvs, dmid_f32=buf("lm_dh", (Mlp, H)), dx_f32=buf("lm_dh1", (Mlp, H)), dN=dN, dx_bf16=dN,
+                 dctx=buf("lm_dctx", (Mlp, H), bf))
+        if self.LM_WGRAD_BATCHED and "lm_act_all" in ws and self.params.gr(self.ll[0].fw) is not None:
             # dY operands of every layer stay alive until their group's batched weight-gradient launches
-            dhb_all = self._stack(ws, "lm_dhb", nl, (Mlp, H), bf); dh1b_all = self._stack(ws, "lm_dh1b", nl, (Mlp, H), bf)
-            ldU_all = self._stack(ws, "lm_dU", nl, (Mlp, FF), bf); ldqkv_all = self._stack(ws, "lm_dqkv", nl, (Mlp, 3 * H), bf)
-            group = self._wgrad_group_size(nl, after_layer)
+            dY = (self._stack(ws, "lm_dhb", nl, (Mlp, H), bf), self._stack(ws, "lm_dU", nl, (Mlp, FF), bf),
+                  self._stack(ws, "lm_dh1b", nl, (Mlp, H), bf), self._stack(ws, "lm_dqkv", nl, (Mlp, 3 * H), bf))
+            grp = self._wgrad_groups(ws, "lm", self.ll, after_layer, dY,
+                                     ("lm_act_all", "lm_y1b_all", "lm_ctx_all", "lm_yb_all"), Mlp, Ml)
         else:
-            dhb = buf("lm_dhb", (Mlp, H), bf); dh1b = buf("lm_dh1b", (Mlp, H), bf)
-            ldU = buf("lm_dU", (Mlp, FF), bf); ldqkv = buf("lm_dqkv", (Mlp, 3 * H), bf)
-        ldN = buf("lm_dN", (Mlp, H), bf); ldctx = buf("lm_dctx", (Mlp, H), bf)
+            d.update(dmid_bf16=buf("lm_dhb", (Mlp, H), bf), dh1_bf16=buf("lm_dh1b", (Mlp, H), bf),
+                     dU=buf("lm_dU", (Mlp, FF), bf), dqkv=buf("lm_dqkv", (Mlp, 3 * H), bf))
         # (the LM has attention dropout: it needs all three thirds of the QKV bias gradient - in-kernel partial sums of three
         #  tiles per wave cost the S <= 64 kernel 11 us per launch against the 10 us per layer of the batched pass over dqkv:
         #  LM_BIAS_PARTIALS stays off; the form is exercised by tests/test_gpu_ops.py)
         lparts = None
-        if self.LM_BIAS_PARTIALS and batched and not ws.get("lm_stage"):
+        if self.LM_BIAS_PARTIALS and grp and not staged:
             npart = ops.attention_bwd_partials(B, T, H, heads, 3)
             if npart:
                 lparts = (self._stack(ws, "lm_qbpart", nl, (npart, 3 * H), torch.float32), npart)
-        dyb = None          # bf16 part of d y2 (from the next layer's QKV dgrad)
-        dyf = dvs           # f32 part of d y2
-        embed_done = False
+        embed_done = []
 
-        def embed_backward(dyb_, dyf_):
-            # embeddings: y0 = dropout(LN(esum))
-            desum = buf("lm_desum", (Mlp, H))
-            ops.layernorm_bwd(ws["lm_esum"], ws["lm_emean"], ws["lm_erstd"], P.w("bert.embeddings.LayerNorm.weight"), Ml, H,
-                              dy_bf16=dyb_, dy_f32=dyf_, dx_f32=desum, dgamma=P.gr("bert.embeddings.LayerNorm.weight"),
-                              dbeta=P.gr("bert.embeddings.LayerNorm.bias"), drop=self._drop(pdh, 1, True), drop_on_dy=True)
-            if ws.get("txt_embeds") is not None:
-                ws["d_inputs_embeds"] = desum[:Ml].view(B, T, H)
-            ops.scatter_add(desum, [None if ws.get("txt_embeds") is not None else
-                                    (P.gr("bert.embeddings.word_embeddings.weight"), ws["ids"]),
-                                    (P.gr("bert.embeddings.position_embeddings.weight"), ws["lm_pos"]),
-                                    (P.gr("bert.embeddings.token_type_embeddings.weight"), ws["lm_tt"])], Ml, H,
-                            rowmask=amf)   # padded positions are masked keys everywhere: their gradient is exactly 0
+        def embed_ahead():
+            # data-parallel step: the embedding tables' gradient (a third of the bytes on the wire) first, so that its
+            # all-reduce runs under the last group's weight-gradient launches (train.BucketReducer)
+            self._lm_embed_backward(ws, d["dy_bf16"], d["dy_f32"])
+            embed_done.append(True)
+            note("lm_embed")
         ops.pycall(lambda: self._prof_begin("lm_bwd"))
         for i in reversed(range(nl)):
-            ln = self.ll[i]
-            g = lambda k: ws[f"lm_{k}{i}"]  # noqa: E731
-            if batched:
-                dhb, dh1b, ldU, ldqkv = dhb_all[i], dh1b_all[i], ldU_all[i], ldqkv_all[i]
-            if ws.get("lm_stage"):
-                a = ws[f"stage_lm{i}"]
-                a.drop_seed = self.drop_seed & 0xFFFFFFFF
-                gb = ops.layer_bwd_args(
-                    a, dy_bf16=dyb, dy_f32=dyf, dx_f32=dh1, dx_bf16=ldN, dU=ldU, dN=ldN, dctx=ldctx, dqkv=ldqkv,
-                    dmid_bf16=dhb, dh1_bf16=dh1b, dmid_f32=dh, do_wgrad=0 if batched else 1,
-                    g_wqkv=P.gr(ln.qw, n_elems=3 * H * H, shape=(3 * H, H)),
-                    g_bqkv=None if batched else P.gr(ln.qb, n_elems=3 * H, shape=(3 * H,)),
-                    g_wo=P.gr(ln.ow), g_bo=P.gr(ln.ob), g_wi=P.gr(ln.iw), g_bi=P.gr(ln.ib), g_wf=P.gr(ln.fw), g_bf=P.gr(ln.fb),
-                    g_ln1w=P.gr(ln.ln1w), g_ln1b=P.gr(ln.ln1b), g_ln2w=P.gr(ln.ln2w), g_ln2b=P.gr(ln.ln2b))
-                ws[f"stage_lm_bwd{i}"] = gb
-                ops.layer_call("vault_lm_layer_bwd", gb, seeded=bool(a.attn_drop_thresh or a.hid_drop_thresh))
-                dyb, dyf = ldN, dh1
-                if not batched:
-                    note(f"lm{i}")
-                elif i % group == 0:
-                    hi = min(nl, i + group)
-                    if i == 0 and after_layer is not None:
-                        # data-parallel step: the embedding tables' gradient (a third of the bytes on the wire) first, so
-                        # that its all-reduce runs under the last group's weight-gradient launches (train.BucketReducer)
-                        embed_backward(dyb, dyf)
-                        embed_done = True
-                        note("lm_embed")
-                    def launch(i=i, hi=hi):
-                        self._qkv_bias_grads_batched(ldqkv_all, self.ll, i, hi, 3 * H, Ml, 3 * H)
-                        self._wgrad_group(((dhb_all, ws["lm_act_all"], "fw", H, FF), (ldU_all, ws["lm_y1b_all"], "iw", FF, H),
-                                           (dh1b_all, ws["lm_ctx_all"], "ow", H, H), (ldqkv_all, ws["lm_yb_all"], "qw", 3 * H, H)),
-                                          self.ll, i, hi, Mlp, Ml)
-                    self._wgrads_aside(launch, after_layer)
-                    for j in reversed(range(i, hi)):
-                        note(f"lm{j}")
-                continue
-            # y2 = LN2(h2)
-            ops.layernorm_bwd(g("h2"), g("m2"), g("r2"), P.w(ln.ln2w), Ml, H, dy_bf16=dyb, dy_f32=dyf, dx_f32=dh,
-                              dx_bf16=dhb, dgamma=P.gr(ln.ln2w), dbeta=P.gr(ln.ln2b),
-                              drop=self._drop(pdh, 16 * i + 4, True), dbias=P.gr(ln.fb))
-            self._dgrad(dhb, ln.fw, ldU, Mlp, FF, H, ops.EPI_BF16_DGELU, Ml, aux=g("u"), colsum=P.gr(ln.ib))
-            if not batched:
-                self._wgrad(dhb, g("act"), ln.fw, None, Mlp, H, FF, Ml)
-            self._dgrad(ldU, ln.iw, ldN, Mlp, H, FF, ops.EPI_BF16, Ml)
-            if not batched:
-                self._wgrad(ldU, g("y1b"), ln.iw, None, Mlp, FF, H, Ml)
-            # y1 = LN1(h1) ; d y1 = dgrad(bf16) + dh (residual)
-            ops.layernorm_bwd(g("h1"), g("m1"), g("r1"), P.w(ln.ln1w), Ml, H, dy_bf16=ldN, dy_f32=dh, dx_f32=dh1,
-                              dx_bf16=dh1b, dgamma=P.gr(ln.ln1w), dbeta=P.gr(ln.ln1b),
-                              drop=self._drop(pdh, 16 * i + 3, True), dbias=P.gr(ln.ob))
-            self._dgrad(dh1b, ln.ow, ldctx, Mlp, H, H, ops.EPI_BF16, Ml)
-            if not batched:
-                self._wgrad(dh1b, g("ctx"), ln.ow, None, Mlp, H, H, Ml)
-            lhm = ws.get("lm_qkv_hm", 0)
-            ops.attention_bwd(g("qkv"), amf, g("ctx"), g("lse"), ldctx, ldqkv, B, T, H, heads,
-                              drop=self._drop(pda, 16 * i + 2, True), qkv_hm=lhm,
-                              **(dict(bias_partials=lparts[0][i], bias_thirds=3) if lparts else {}))
-            self._dgrad(ldqkv, ln.qw, ldN, Mlp, H, 3 * H, ops.EPI_BF16, Ml, **(dict(a_hm=lhm) if lhm else {}))
-            if not batched:
-                self._wgrad(ldqkv, yb[i], ln.qw, ln.qb, Mlp, 3 * H, H, Ml)
-            # (batched: the QKV bias gradient with the group's launches below)
-            dyb, dyf = ldN, dh1   # consumed by the next iteration's LN2 backward before being overwritten
-            if not batched:
-                note(f"lm{i}")
-            elif i % group == 0:
-                # the weight gradients of layers i .. hi - 1, one launch per kind (dY, X: slices i.. of the stacks)
-                hi = min(nl, i + group)
-                if i == 0 and after_layer is not None:     # (data-parallel step: embedding gradient first, see above)
-                    embed_backward(dyb, dyf)
-                    embed_done = True
-                    note("lm_embed")
-                def launch(i=i, hi=hi, lhm=lhm):
-                    self._qkv_bias_grads_batched(ldqkv_all, self.ll, i, hi, 3 * H, Ml, 3 * H, hm=lhm, parts=lparts)
-                    self._wgrad_group(((dhb_all, ws["lm_act_all"], "fw", H, FF), (ldU_all, ws["lm_y1b_all"], "iw", FF, H),
-                                       (dh1b_all, ws["lm_ctx_all"], "ow", H, H), (ldqkv_all, ws["lm_yb_all"], "qw", 3 * H, H, lhm)),
-                                      self.ll, i, hi, Mlp, Ml)
-                self._wgrads_aside(launch, after_layer)
-                for j in reversed(range(i, hi)):
-                    note(f"lm{j}")
+            if grp:
+                d["dmid_bf16"], d["dU"], d["dh1_bf16"], d["dqkv"] = (t[i] for t in dY)
+            if staged:
+                self._layer_bwd_staged(ws, "lm", self.ll, i, d, bool(grp))
+            else:
+                self._lm_layer_bwd(ws, i, d, bool(grp), lparts)
+            d["dy_bf16"], d["dy_f32"] = d["dN"], d["dx_f32"]
+            # (the stage calls keep dqkv row-major: lm_qkv_hm is 0 there)
+            self._layer_done("lm", grp, i, note, after_layer, hm=ws.get("lm_qkv_hm", 0), parts=lparts,
+                             ahead=embed_ahead if (i == 0 and after_layer is not None) else None)
         ops.pycall(lambda: self._prof_end("lm_bwd"))
         if not embed_done:
-            embed_backward(dyb, dyf)
+            self._lm_embed_backward(ws, d["dy_bf16"], d["dy_f32"])
         self._join_wgrads()
         if not embed_done:
             note("lm_embed")
-        self._run_census(ws, "backward")
 
+    def _lm_embed_backward(self, ws, dyb, dyf):
+        # embeddings: y0 = dropout(LN(esum))
+        P = self.params
+        B, T, H, Ml, Mlp = (ws[k] for k in ("B", "T", "H", "Ml", "Mlp"))
+        desum = self._buf(ws, "lm_desum", (Mlp, H), torch.float32)
+        ops.layernorm_bwd(ws["lm_esum"], ws["lm_emean"], ws["lm_erstd"], P.w("bert.embeddings.LayerNorm.weight"), Ml, H,
+                          dy_bf16=dyb, dy_f32=dyf, dx_f32=desum, dgamma=P.gr("bert.embeddings.LayerNorm.weight"),
+                          dbeta=P.gr("bert.embeddings.LayerNorm.bias"),
+                          drop=self._drop(self.spec.lm.hidden_dropout_prob, 1, True), drop_on_dy=True)
+        if ws.get("txt_embeds") is not None:
+            ws["d_inputs_embeds"] = desum[:Ml].view(B, T, H)
+        ops.scatter_add(desum, [None if ws.get("txt_embeds") is not None else
+                                (P.gr("bert.embeddings.word_embeddings.weight"), ws["ids"]),
+                                (P.gr("bert.embeddings.position_embeddings.weight"), ws["lm_pos"]),
+                                (P.gr("bert.embeddings.token_type_embeddings.weight"), ws["lm_tt"])], Ml, H,
+                        rowmask=ws["amf"])   # padded positions are masked keys everywhere: their gradient is exactly 0
+
+    def _lm_layer_bwd(self, ws, i, d, deferred, lparts):
+        """The layer backward kernel by kernel (``deferred``: without its weight gradients)."""
+        P, ln, lm, lhm = self.params, self.ll[i], self.spec.lm, ws.get("lm_qkv_hm", 0)
+        B, T, H, FF, heads, Ml, Mlp = (ws[k] for k in ("B", "T", "H", "FF", "heads", "Ml", "Mlp"))
+        pdh, pda = lm.hidden_dropout_prob, lm.attention_probs_dropout_prob
+        g = lambda k: ws[f"lm_{k}{i}"]  # noqa: E731
+        wgrad = (lambda *a: None) if deferred else self._wgrad      # (deferred: with the group's launches, _layer_done)
+        dh, dh1, dhb, dh1b, dU, dqkv, dN, dctx = (d[k] for k in ("dmid_f32", "dx_f32", "dmid_bf16", "dh1_bf16", "dU", "dqkv", "dN", "dctx"))
+        # y2 = LN2(h2)
+        ops.layernorm_bwd(g("h2"), g("m2"), g("r2"), P.w(ln.ln2w), Ml, H, dy_bf16=d["dy_bf16"], dy_f32=d["dy_f32"], dx_f32=dh,
+                          dx_bf16=dhb, dgamma=P.gr(ln.ln2w), dbeta=P.gr(ln.ln2b),
+                          drop=self._drop(pdh, 16 * i + 4, True), dbias=P.gr(ln.fb))
+        self._dgrad(dhb, ln.fw, dU, Mlp, FF, H, ops.EPI_BF16_DGELU, Ml, aux=g("u"), colsum=P.gr(ln.ib))
+        wgrad(dhb, g("act"), ln.fw, None, Mlp, H, FF, Ml)
+        self._dgrad(dU, ln.iw, dN, Mlp, H, FF, ops.EPI_BF16, Ml)
+        wgrad(dU, g("y1b"), ln.iw, None, Mlp, FF, H, Ml)
+        # y1 = LN1(h1) ; d y1 = dgrad(bf16) + dh (residual)
+        ops.layernorm_bwd(g("h1"), g("m1"), g("r1"), P.w(ln.ln1w), Ml, H, dy_bf16=dN, dy_f32=dh, dx_f32=dh1,
+                          dx_bf16=dh1b, dgamma=P.gr(ln.ln1w), dbeta=P.gr(ln.ln1b),
+                          drop=self._drop(pdh, 16 * i + 3, True), dbias=P.gr(ln.ob))
+        self._dgrad(dh1b, ln.ow, dctx, Mlp, H, H, ops.EPI_BF16, Ml)
+        wgrad(dh1b, g("ctx"), ln.ow, None, Mlp, H, H, Ml)
+        ops.attention_bwd(g("qkv"), ws["amf"], g("ctx"), g("lse"), dctx, dqkv, B, T, H, heads,
+                          drop=self._drop(pda, 16 * i + 2, True), qkv_hm=lhm,
+                          **(dict(bias_partials=lparts[0][i], bias_thirds=3) if lparts else {}))
+        self._dgrad(dqkv, ln.qw, dN, Mlp, H, 3 * H, ops.EPI_BF16, Ml, **(dict(a_hm=lhm) if lhm else {}))
+        wgrad(dqkv, ws["lm_yb"][i], ln.qw, ln.qb, Mlp, 3 * H, H, Ml)

@@ -336,7 +336,6 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
     WGRAD_BESIDE_LM_ITEMS = 0
     WGRAD_SIDE_ITEMS = 224         # items per grouped launch on the second stream (B = 64, same box: 256: 13.50 / 13.59 ms, 224: 13.32 / 13.46, 192: 13.23 / 13.47, 160: 13.63 / 13.53)
 
-
     def _plan_gelu8(self, ws, n2, act, u, ln, Mp, M):
         """Kernel configuration (5 / 6) on which BOTH the FFN-in forward and the gelu'-product data gradient of this ViLT
         workspace run with the 8-bit tile-native gelu' (vault_gemm aux_u8: an opaque image only the same kernel and shape reads
@@ -444,7 +443,6 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
             return self._forward(batch, train, labels, need_hidden, loss_scale, precise, ws_tag, image_token_type_idx,
                                  advance_seed)
 
-
     def _forward(self, batch, train, labels, need_hidden, loss_scale, precise=False, ws_tag=0, image_type_idx=1,
                  advance_seed=True):
         # (precise + train: split-bf16 FORWARD GEMMs - logits / loss at fp32 class - with the bf16 backward; every operand the
@@ -466,119 +464,29 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
         spec, P = self.spec, self.params
         v = spec.vilt
         train = ws["train"]
-        B, T, S, M, Mp, H, FF, heads, NP = (ws[k] for k in ("B", "T", "S", "M", "Mp", "H", "FF", "heads", "NP"))
-        ids, tt, amf, pix, labels, km = ws["ids"], ws["tt"], ws["amf"], ws["pix"], ws["labels"], ws["keymask"]
+        B, T, S, Mp, H, NP = (ws[k] for k in ("B", "T", "S", "Mp", "H", "NP"))
+        ids, tt, pix, labels, km = ws["ids"], ws["tt"], ws["pix"], ws["labels"], ws["keymask"]
         buf = lambda name, shape, dtype=torch.float32: self._buf(ws, name, shape, dtype)  # noqa: E731
         bf = self.hdt
         ws["drop_seed"] = self.drop_seed
         pr = precise
         W3 = 3 if pr else 1   # operand width multiplier of the split-bf16 path
-        pt = pr and train     # precise forward of a training step: the plain bf16 operands of the backward are kept beside the split ones
         if pr:
-            if pt:
+            if train:   # precise forward of a training step: the plain bf16 operands of the backward are kept beside the split ones
                 self.params._pb3_fresh = False   # (a recorded train step must carry the re-split of the weights the optimizer just wrote)
             self.params.ensure_split3()
         if self.fp8_forward and not pr:
             self._fp8_refresh_weights()
 
-        # ------------------------------ language model ------------------------------
+        Ml, Mlp = B * T, _pad(B * T)
+        ws.update(Ml=Ml, Mlp=Mlp)
         if spec.lm is not None:
-            lm = spec.lm
-            Ml, Mlp = B * T, _pad(B * T)
-            ws.update(Ml=Ml, Mlp=Mlp)
-            lm_tt = tt if (tt is not None and lm.type_vocab_size >= 2) else 0   # ref: model.py:174-180
-            ws["lm_tt"] = lm_tt
-            pos = buf("lm_pos", (B, T), torch.int32)
-            ops.position_ids(ids, pos, B, T, 1 if lm.kind == "roberta" else 0, lm.pad_token_id)
-            esum = buf("lm_esum", (Mlp, H))
-            te = ws.get("txt_embeds")
-            ops.gather_sum(te, esum, [None if te is not None else (P.w("bert.embeddings.word_embeddings.weight"), ids),
-                                      (P.w("bert.embeddings.position_embeddings.weight"), pos),
-                                      (P.w("bert.embeddings.token_type_embeddings.weight"), lm_tt)], Ml, H)
-            keep = train and not self.freeze_lm
-            nl = lm.num_hidden_layers
-            if keep and self.LM_WGRAD_BATCHED and H % 128 == 0 and FF % 128 == 0:
-                # X operands of the deferred, batched weight gradients: one tensor per kind, a layer per slice
-                self._stack(ws, "lm_yb", nl + 1, (Mlp, H), bf)
-                for base, width in (("lm_ctx", H), ("lm_y1b", H), ("lm_act", FF)):
-                    self._stack(ws, base, nl, (Mlp, width), bf)
-            y = [buf(f"lm_y{i}" if keep else f"lm_y{i % 2}", (Mlp, H)) for i in range(nl + 1)]
-            yb = [buf((f"lm_yb{i}" if keep else f"lm_yb{i % 2}") + ("_3" if pr else ""), (Mlp, W3 * H), bf)
-                  for i in range(nl + 1)]
-            ybs = [buf(f"lm_yb{i}" if keep else f"lm_yb{i % 2}", (Mlp, H), bf) for i in range(nl + 1)] if pt else None
-            lm_train = train   # dropout stays active in a frozen LM too (ref: model.py:189 only disables grad)
-            pdh, pda = lm.hidden_dropout_prob, lm.attention_probs_dropout_prob
-            q8l = self._fp8_scratch(Mlp, H) if (self.fp8_forward and not pr and Mlp % 256 == 0) else (None, None)
-            ops.layernorm_fwd(esum, P.w("bert.embeddings.LayerNorm.weight"), P.w("bert.embeddings.LayerNorm.bias"),
-                              lm.layer_norm_eps, Ml, H, y_f32=y[0], y_bf16=(ybs[0] if pt else None) if pr else yb[0],
-                              y_split3=yb[0] if pr else None, mean=buf("lm_emean", (Mlp,)),
-                              rstd=buf("lm_erstd", (Mlp,)), drop=self._drop(pdh, 1, lm_train),
-                              y_q=q8l[0], y_scale=q8l[1])
-            lm_stage = self._use_stage(Mlp, pr)
-            ws["lm_stage"] = lm_stage
-            ops.pycall(lambda: self._prof_begin("lm_fwd"))
-            for i, ln in enumerate(self.ll):
-                sfx = f"{i}" if keep else ""
-                qkv = buf(f"lm_qkv{sfx}", (Mlp, 3 * H), bf)
-                p3 = "_3" if pr else ""
-                ctx = buf(f"lm_ctx{sfx}{p3}", (Mlp, W3 * H), bf)
-                lse = buf(f"lm_lse{sfx}", (B, heads, T))
-                h1 = buf(f"lm_h1{sfx}", (Mlp, H)); y1 = buf(f"lm_y1{sfx}", (Mlp, H))
-                y1b = buf(f"lm_y1b{sfx}{p3}", (Mlp, W3 * H), bf)
-                u = buf(f"lm_u{sfx}", (Mlp, FF), bf) if keep else None
-                act = buf(f"lm_act{sfx}{p3}", (Mlp, W3 * FF), bf)
-                h2 = buf(f"lm_h2{sfx}", (Mlp, H))
-                if lm_stage:
-                    ws["lm_qkv_hm"], ws["lm_qkv_hm_mode"] = 0, None
-                    da, dh = self._drop(pda, 16 * i + 2, lm_train), self._drop(pdh, 16 * i + 3, lm_train)
-                    a = self._stage_layer_args(
-                        ws, ln, "lm", i, Ml, Mlp, T, amf, y[i], y[i + 1],
-                        dict(qkv=qkv, ctx=ctx, lse=lse, xm=h1, y1=y1, n2=y1b, act=act, u=u, h2=h2,
-                             m1=buf(f"lm_m1{sfx}", (Mlp,)), r1=buf(f"lm_r1{sfx}", (Mlp,)),
-                             m2=buf(f"lm_m2{sfx}", (Mlp,)), r2=buf(f"lm_r2{sfx}", (Mlp,))),
-                        drops=(da, dh), x_in_bf16=yb[i], x_out_bf16=yb[i + 1])
-                    ops.layer_call("vault_lm_layer_fwd", a, seeded=bool(da.thresh or dh.thresh))
-                    continue
-                lhm = self._plan_head_major(ws, "lm_qkv_hm", yb[i], ln.qw, Mlp, Ml, T, pr, keep)
-                self._linear(yb[i], ln.qw, qkv, Mlp, 3 * H, H, ops.EPI_BF16, Ml,
-                             bias=P.w(ln.qb, n_elems=3 * H, shape=(3 * H,)), precise=pr, prequant=q8l[0] is not None,
-                             **(dict(out_hm=lhm) if lhm else {}))
-                ops.attention_fwd(qkv, amf, None if pr else ctx, lse, B, T, H, heads,
-                                  drop=self._drop(pda, 16 * i + 2, lm_train), ctx_split3=ctx if pr else None, qkv_hm=lhm)
-                if pt:
-                    self._keep_hi(ctx, buf(f"lm_ctx{sfx}", (Mlp, H), bf), H)
-                self._linear(ctx, ln.ow, h1, Mlp, H, H, ops.EPI_F32_RES, Ml, bias=P.w(ln.ob), res=y[i],
-                             drop=self._drop(pdh, 16 * i + 3, lm_train), precise=pr)
-                ops.layernorm_fwd(h1, P.w(ln.ln1w), P.w(ln.ln1b), lm.layer_norm_eps, Ml, H, y_f32=y1,
-                                  y_bf16=(buf(f"lm_y1b{sfx}", (Mlp, H), bf) if pt else None) if pr else y1b,
-                                  y_split3=y1b if pr else None,
-                                  mean=buf(f"lm_m1{sfx}", (Mlp,)), rstd=buf(f"lm_r1{sfx}", (Mlp,)),
-                                  y_q=q8l[0], y_scale=q8l[1])
-                ops.pycall(lambda: self._prof_begin("ffn1"))
-                # (the epilogue addresses gelu' with the row stride of its main output: in the split form a [rows, 3 FF] buffer
-                #  whose first third is written)
-                u_out = buf(f"lm_u{sfx}_3", (Mlp, W3 * FF), bf) if (pt and u is not None) else u
-                actq = self._linear(y1b, ln.iw, act, Mlp, FF, H, ops.EPI_BF16_GELU, Ml, bias=P.w(ln.ib), out2=u_out, precise=pr,
-                                    split3=pr, ldo=W3 * FF, prequant=q8l[0] is not None or None, emit_q=self.FFN_OUT_FP8)
-                if pt:
-                    self._keep_hi(act, buf(f"lm_act{sfx}", (Mlp, FF), bf), FF)
-                    if u is not None:
-                        self._keep_hi(u_out, u, FF)
-                fl_l = 2.0 * Ml * FF * H * W3
-                ops.pycall(lambda: self._prof_end("ffn1", fl_l))
-                self._linear(act, ln.fw, h2, Mlp, H, FF, ops.EPI_F32_RES, Ml, bias=P.w(ln.fb), res=y1,
-                             drop=self._drop(pdh, 16 * i + 4, lm_train), precise=pr, prequant=bool(actq))
-                ops.layernorm_fwd(h2, P.w(ln.ln2w), P.w(ln.ln2b), lm.layer_norm_eps, Ml, H, y_f32=y[i + 1],
-                                  y_bf16=(ybs[i + 1] if pt else None) if pr else yb[i + 1], y_split3=yb[i + 1] if pr else None,
-                                  mean=buf(f"lm_m2{sfx}", (Mlp,)), rstd=buf(f"lm_r2{sfx}", (Mlp,)),
-                                  y_q=q8l[0], y_scale=q8l[1])
-            ops.pycall(lambda: self._prof_end("lm_fwd"))
-            text_src = y[nl]
+            ws["lm_y"], ws["lm_yb"] = self._lm_forward(ws, pr, buf, bf)
+            text_src = ws["lm_y"][-1]
             use_pos = spec.use_vilt_position_embeddings
             tables = [(P.w("embeddings.text_embeddings.token_type_embeddings.weight"), tt if tt is not None else 0)]
         else:
-            Ml, Mlp = B * T, _pad(B * T)
-            ws.update(Ml=Ml, Mlp=Mlp)
+            ws["lm_y"] = ws["lm_yb"] = None
             text_src = ws.get("txt_embeds")        # inputs_embeds replace ViLT's own word-embedding lookup
             use_pos = True
             tables = [(P.w("embeddings.text_embeddings.token_type_embeddings.weight"), tt if tt is not None else 0),
@@ -604,8 +512,110 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
             ops.rows_add(ws["img_embeds"], mt[ws.get("img_type", 1)], x[0], B * NP, H, NP, S, T)
         else:
             self._patch_embed_forward(ws, x, mt, pix, pr, W3, Kp, Mpp, buf, bf)
-        ws["lm_y"], ws["lm_yb"] = (y if spec.lm is not None else None), ((ybs if pt else yb) if spec.lm is not None else None)
         return self._forward_encoder(ws, x, need_hidden, loss_scale, pr, W3, labels, km, train, buf, bf)
+
+    def _ln_y16(self, ws, pr, y16, name, shape):
+        """`y_bf16` of a LayerNorm that feeds a Linear: the operand ``y16`` itself; in the precise mode (the operand is `y_split3`)
+        only a training step keeps the plain 16-bit form, in buffer ``name``: what the bf16 backward reads."""
+        return y16 if not pr else (self._buf(ws, name, shape, self.hdt) if ws["train"] else None)
+
+    def _ffn_forward(self, ws, a16, ln, pre, sfx, rows, rows_pad, res, out, u, act, pr, prequant, drop=NO_DROP, g8=None):
+        """act = gelu(a16 . Wi^T + bi) with gelu' into ``u`` (training), out = res + dropout(act . Wf^T + bf).  ``pre`` + name + ``sfx``:
+        workspace names; ``g8``: _plan_gelu8.  Returns FFN-out's `prequant`: whether FFN-in's epilogue wrote its MXFP8 image."""
+        P, H, FF, bf, W3, pt = self.params, ws["H"], ws["FF"], self.hdt, (3 if pr else 1), pr and ws["train"]
+        ops.pycall(lambda: self._prof_begin("ffn1"))
+        # (the epilogue addresses gelu' with the row stride of its main output: in the split form a [rows, 3 FF] buffer
+        #  whose first third is written)
+        u_out = self._buf(ws, f"{pre}u{sfx}_3", (rows_pad, W3 * FF), bf) if (pt and u is not None) else u
+        actq = self._linear(a16, ln.iw, act, rows_pad, FF, H, ops.EPI_BF16_GELU, rows, bias=P.w(ln.ib), out2=u_out, precise=pr,
+                            split3=pr, ldo=W3 * FF, prequant=prequant, emit_q=self.FFN_OUT_FP8,
+                            **(dict(cfg=g8, aux_u8=True) if g8 is not None else {}))
+        if pt:
+            self._keep_hi(act, self._buf(ws, f"{pre}act{sfx}", (rows_pad, FF), bf), FF)
+            if u is not None:
+                self._keep_hi(u_out, u, FF)
+        ops.pycall(lambda: self._prof_end("ffn1", 2.0 * rows * FF * H * W3))
+        self._linear(act, ln.fw, out, rows_pad, H, FF, ops.EPI_F32_RES, rows, bias=P.w(ln.fb), res=res, drop=drop, precise=pr,
+                     prequant=bool(actq))
+        return bool(actq)
+
+    def _lm_forward(self, ws, pr, buf, bf):
+        """The LM stack: returns its f32 outputs y[0 .. layers] and their plain 16-bit forms (the QKV weight gradients' X operands)."""
+        P, lm, train, ids, tt, amf = self.params, self.spec.lm, ws["train"], ws["ids"], ws["tt"], ws["amf"]
+        B, T, H, FF, heads, Ml, Mlp = (ws[k] for k in ("B", "T", "H", "FF", "heads", "Ml", "Mlp"))
+        W3, pt = (3 if pr else 1), pr and train
+        lm_tt = ws["lm_tt"] = tt if (tt is not None and lm.type_vocab_size >= 2) else 0   # ref: model.py:174-180
+        pos = buf("lm_pos", (B, T), torch.int32)
+        ops.position_ids(ids, pos, B, T, 1 if lm.kind == "roberta" else 0, lm.pad_token_id)
+        esum = buf("lm_esum", (Mlp, H))
+        te = ws.get("txt_embeds")
+        ops.gather_sum(te, esum, [None if te is not None else (P.w("bert.embeddings.word_embeddings.weight"), ids),
+                                  (P.w("bert.embeddings.position_embeddings.weight"), pos),
+                                  (P.w("bert.embeddings.token_type_embeddings.weight"), lm_tt)], Ml, H)
+        keep = train and not self.freeze_lm
+        nl = lm.num_hidden_layers
+        if keep and self.LM_WGRAD_BATCHED and H % 128 == 0 and FF % 128 == 0:
+            # X operands of the deferred, batched weight gradients: one tensor per kind, a layer per slice
+            self._stack(ws, "lm_yb", nl + 1, (Mlp, H), bf)
+            for base, width in (("lm_ctx", H), ("lm_y1b", H), ("lm_act", FF)):
+                self._stack(ws, base, nl, (Mlp, width), bf)
+        ybn = [f"lm_yb{i}" if keep else f"lm_yb{i % 2}" for i in range(nl + 1)]
+        y = [buf(f"lm_y{i}" if keep else f"lm_y{i % 2}", (Mlp, H)) for i in range(nl + 1)]
+        yb = [buf(n + ("_3" if pr else ""), (Mlp, W3 * H), bf) for n in ybn]
+        lm_train = train   # dropout stays active in a frozen LM too (ref: model.py:189 only disables grad)
+        pdh, pda = lm.hidden_dropout_prob, lm.attention_probs_dropout_prob
+        q8l = self._fp8_scratch(Mlp, H) if (self.fp8_forward and not pr and Mlp % 256 == 0) else (None, None)
+        ops.layernorm_fwd(esum, P.w("bert.embeddings.LayerNorm.weight"), P.w("bert.embeddings.LayerNorm.bias"),
+                          lm.layer_norm_eps, Ml, H, y_f32=y[0], y_bf16=self._ln_y16(ws, pr, yb[0], ybn[0], (Mlp, H)),
+                          y_split3=yb[0] if pr else None, mean=buf("lm_emean", (Mlp,)),
+                          rstd=buf("lm_erstd", (Mlp,)), drop=self._drop(pdh, 1, lm_train),
+                          y_q=q8l[0], y_scale=q8l[1])
+        lm_stage = ws["lm_stage"] = self._use_stage(Mlp, pr)
+        ops.pycall(lambda: self._prof_begin("lm_fwd"))
+        for i, ln in enumerate(self.ll):
+            sfx = f"{i}" if keep else ""
+            qkv = buf(f"lm_qkv{sfx}", (Mlp, 3 * H), bf)
+            p3 = "_3" if pr else ""
+            ctx = buf(f"lm_ctx{sfx}{p3}", (Mlp, W3 * H), bf)
+            lse = buf(f"lm_lse{sfx}", (B, heads, T))
+            h1 = buf(f"lm_h1{sfx}", (Mlp, H)); y1 = buf(f"lm_y1{sfx}", (Mlp, H))
+            y1b = buf(f"lm_y1b{sfx}{p3}", (Mlp, W3 * H), bf)
+            u = buf(f"lm_u{sfx}", (Mlp, FF), bf) if keep else None
+            act = buf(f"lm_act{sfx}{p3}", (Mlp, W3 * FF), bf)
+            h2 = buf(f"lm_h2{sfx}", (Mlp, H))
+            if lm_stage:
+                ws["lm_qkv_hm"], ws["lm_qkv_hm_mode"] = 0, None
+                da, dh = self._drop(pda, 16 * i + 2, lm_train), self._drop(pdh, 16 * i + 3, lm_train)
+                a = self._stage_layer_args(
+                    ws, ln, "lm", i, Ml, Mlp, T, amf, y[i], y[i + 1],
+                    dict(qkv=qkv, ctx=ctx, lse=lse, xm=h1, y1=y1, n2=y1b, act=act, u=u, h2=h2,
+                         m1=buf(f"lm_m1{sfx}", (Mlp,)), r1=buf(f"lm_r1{sfx}", (Mlp,)),
+                         m2=buf(f"lm_m2{sfx}", (Mlp,)), r2=buf(f"lm_r2{sfx}", (Mlp,))),
+                    drops=(da, dh), x_in_bf16=yb[i], x_out_bf16=yb[i + 1])
+                ops.layer_call("vault_lm_layer_fwd", a, seeded=bool(da.thresh or dh.thresh))
+                continue
+            lhm = self._plan_head_major(ws, "lm_qkv_hm", yb[i], ln.qw, Mlp, Ml, T, pr, keep)
+            self._linear(yb[i], ln.qw, qkv, Mlp, 3 * H, H, ops.EPI_BF16, Ml,
+                         bias=P.w(ln.qb, n_elems=3 * H, shape=(3 * H,)), precise=pr, prequant=q8l[0] is not None,
+                         **(dict(out_hm=lhm) if lhm else {}))
+            ops.attention_fwd(qkv, amf, None if pr else ctx, lse, B, T, H, heads,
+                              drop=self._drop(pda, 16 * i + 2, lm_train), ctx_split3=ctx if pr else None, qkv_hm=lhm)
+            if pt:
+                self._keep_hi(ctx, buf(f"lm_ctx{sfx}", (Mlp, H), bf), H)
+            self._linear(ctx, ln.ow, h1, Mlp, H, H, ops.EPI_F32_RES, Ml, bias=P.w(ln.ob), res=y[i],
+                         drop=self._drop(pdh, 16 * i + 3, lm_train), precise=pr)
+            ops.layernorm_fwd(h1, P.w(ln.ln1w), P.w(ln.ln1b), lm.layer_norm_eps, Ml, H, y_f32=y1,
+                              y_bf16=self._ln_y16(ws, pr, y1b, f"lm_y1b{sfx}", (Mlp, H)), y_split3=y1b if pr else None,
+                              mean=buf(f"lm_m1{sfx}", (Mlp,)), rstd=buf(f"lm_r1{sfx}", (Mlp,)),
+                              y_q=q8l[0], y_scale=q8l[1])
+            self._ffn_forward(ws, y1b, ln, "lm_", sfx, Ml, Mlp, y1, h2, u, act, pr, q8l[0] is not None or None,
+                              drop=self._drop(pdh, 16 * i + 4, lm_train))
+            ops.layernorm_fwd(h2, P.w(ln.ln2w), P.w(ln.ln2b), lm.layer_norm_eps, Ml, H, y_f32=y[i + 1],
+                              y_bf16=self._ln_y16(ws, pr, yb[i + 1], ybn[i + 1], (Mlp, H)), y_split3=yb[i + 1] if pr else None,
+                              mean=buf(f"lm_m2{sfx}", (Mlp,)), rstd=buf(f"lm_r2{sfx}", (Mlp,)),
+                              y_q=q8l[0], y_scale=q8l[1])
+        ops.pycall(lambda: self._prof_end("lm_fwd"))
+        return y, ([buf(n, (Mlp, H), bf) for n in ybn] if pt else yb)
 
     def _patch_embed_forward(self, ws, x, mt, pix, pr, W3, Kp, Mpp, buf, bf):
         spec, P = self.spec, self.params
@@ -650,7 +660,7 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
     def _forward_encoder(self, ws, x, need_hidden, loss_scale, pr, W3, labels, km, train, buf, bf):
         spec, P = self.spec, self.params
         v = spec.vilt
-        B, T, S, M, Mp, H, FF, heads, NP = (ws[k] for k in ("B", "T", "S", "M", "Mp", "H", "FF", "heads", "NP"))
+        B, S, M, Mp, H, FF, heads = (ws[k] for k in ("B", "S", "M", "Mp", "H", "FF", "heads"))
         nv = v.num_hidden_layers
         # ------------------------------ ViLT encoder ------------------------------
         pt = pr and train
@@ -680,7 +690,8 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
             ws["vilt_stage"] = False
             q8 = self._fp8_scratch(Mp, H) if (self.fp8_forward and not pr and Mp % 256 == 0) else (None, None)
             ops.layernorm_fwd(x[i], P.w(ln.ln1w), P.w(ln.ln1b), v.layer_norm_eps, M, H,
-                              y_bf16=(buf(f"n1{sfx}", (Mp, H), bf) if pt else None) if pr else n1, y_split3=n1 if pr else None, mean=buf(f"m1{sfx}", (Mp,)), rstd=buf(f"r1{sfx}", (Mp,)),
+                              y_bf16=self._ln_y16(ws, pr, n1, f"n1{sfx}", (Mp, H)), y_split3=n1 if pr else None,
+                              mean=buf(f"m1{sfx}", (Mp,)), rstd=buf(f"r1{sfx}", (Mp,)),
                               y_q=q8[0], y_scale=q8[1])
             vhm = self._plan_head_major(ws, "qkv_hm", n1, ln.qw, Mp, M, S, pr, train)
             self._linear(n1, ln.qw, qkv, Mp, 3 * H, H, ops.EPI_BF16, M, bias=P.w(ln.qb, n_elems=3 * H, shape=(3 * H,)),
@@ -690,24 +701,12 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
                 self._keep_hi(ctx, buf(f"ctx{sfx}", (Mp, H), bf), H)
             self._linear(ctx, ln.ow, xm, Mp, H, H, ops.EPI_F32_RES, M, bias=P.w(ln.ob), res=x[i], precise=pr)
             ops.layernorm_fwd(xm, P.w(ln.ln2w), P.w(ln.ln2b), v.layer_norm_eps, M, H,
-                              y_bf16=(buf(f"n2{sfx}", (Mp, H), bf) if pt else None) if pr else n2, y_split3=n2 if pr else None, mean=buf(f"m2{sfx}", (Mp,)), rstd=buf(f"r2{sfx}", (Mp,)),
+                              y_bf16=self._ln_y16(ws, pr, n2, f"n2{sfx}", (Mp, H)), y_split3=n2 if pr else None,
+                              mean=buf(f"m2{sfx}", (Mp,)), rstd=buf(f"r2{sfx}", (Mp,)),
                               y_q=q8[0], y_scale=q8[1])
-            ops.pycall(lambda: self._prof_begin("ffn1"))
             g8 = None if pr else self._plan_gelu8(ws, n2, act, u, ln, Mp, M)
             ws["gelu8_active"] = g8     # what THIS forward stored in `u` (8-bit tile image or plain 16-bit): backward reads this
-            g8kw = dict(cfg=g8, aux_u8=True) if g8 is not None else {}
-            u_out = buf(f"u{sfx}_3", (Mp, W3 * FF), bf) if (pt and u is not None) else u      # (row stride of the main output)
-            actq = self._linear(n2, ln.iw, act, Mp, FF, H, ops.EPI_BF16_GELU, M, bias=P.w(ln.ib), out2=u_out, precise=pr,
-                                split3=pr, ldo=W3 * FF, prequant=q8[0] is not None or None, emit_q=self.FFN_OUT_FP8, **g8kw)
-            if pt:
-                self._keep_hi(act, buf(f"act{sfx}", (Mp, FF), bf), FF)
-                if u is not None:
-                    self._keep_hi(u_out, u, FF)
-            fl_v = 2.0 * M * FF * H * W3
-            ops.pycall(lambda: self._prof_end("ffn1", fl_v))
-            self._linear(act, ln.fw, x[i + 1], Mp, H, FF, ops.EPI_F32_RES, M, bias=P.w(ln.fb), res=xm, precise=pr,
-                         prequant=bool(actq))
-
+            self._ffn_forward(ws, n2, ln, "", sfx, M, Mp, xm, x[i + 1], u, act, pr, q8[0] is not None or None, g8=g8)
         ops.pycall(lambda: self._prof_end("vilt_fwd"))
         # ------------------------------ tail ------------------------------
         out: Dict[str, torch.Tensor] = {}
@@ -722,7 +721,7 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
             Bp = _pad(B)
             ws["Bp"] = Bp
             h0b = buf("h0b_3" if pr else "h0b", (Bp, W3 * H), bf)
-            ops.layernorm_fwd(xl, lw, lb, v.layer_norm_eps, B, H, y_bf16=(buf("h0b", (Bp, H), bf) if pt else None) if pr else h0b,
+            ops.layernorm_fwd(xl, lw, lb, v.layer_norm_eps, B, H, y_bf16=self._ln_y16(ws, pr, h0b, "h0b", (Bp, H)),
                               y_split3=h0b if pr else None, xmap=(1, S, 0), mean=buf("f_mean", (Bp,)),
                               rstd=buf("f_rstd", (Bp,)))
             pre = buf("pool_pre", (Bp, H))

@@ -185,6 +185,10 @@ class Drop:
 NO_DROP = Drop()
 
 
+def _set_drop(a, drop: Drop):      # (the four dropout members of an argument struct)
+    a.drop_thresh, a.drop_seed, a.drop_stream, a.drop_scale = drop.thresh, drop.seed, drop.stream, drop.scale
+
+
 # GEMM scheduling mode (vault_gemm_args.persist): 3 while the GEMMs share the GPU with RCCL collectives on another
 # stream (train.TrainStep sets it for world size > 1): tiles are handed out dynamically / one block per tile, so a CU
 # held by the collective costs its share of throughput instead of a second pass over a static tile list
@@ -210,7 +214,7 @@ def gemm(A, B, out, M, N, K, lda, ldb, ldo, a_mode, b_mode, epi, *, cfg=-1, m_va
     a.rpg, a.gstride, a.goff = rpg, gstride, goff
     a.persist = GEMM_SCHED
     a.batch, a.batch_a, a.batch_b, a.batch_o = batch, batch_a, batch_b, batch_o   # batched weight gradients (ABI 3)
-    a.drop_thresh, a.drop_seed, a.drop_stream, a.drop_scale = drop.thresh, drop.seed, drop.stream, drop.scale
+    _set_drop(a, drop)
     if plan_only:      # the kernel configuration these arguments would run on (vault_gemm_plan): >= 0, or -EINVAL
         return int(L.load(_FMT.get()).vault_gemm_plan(C.byref(a)))
     if _TAPE is not None and _TAPE.rebind_range is not None:
@@ -272,7 +276,7 @@ def gemm_mxfp8(Aq, As, Bq, Bs, out, M, N, K, ldo, epi, *, m_valid=0, bias=None, 
     a.a_mode, a.b_mode, a.epi, a.cfg, a.splits, a.accumulate = 0, 0, epi, cfg, 1, 0
     a.aux_u8, a.out_hm = int(bool(aux_u8)), int(out_hm)
     a.persist = GEMM_SCHED
-    a.drop_thresh, a.drop_seed, a.drop_stream, a.drop_scale = drop.thresh, drop.seed, drop.stream, drop.scale
+    _set_drop(a, drop)
     if plan_only:      # the kernel these arguments would run on (vault_gemm_mxfp8_plan): 0, 5, 6, or -EINVAL
         return int(L.load(_FMT.get()).vault_gemm_mxfp8_plan(C.byref(a)))
     _invoke("vault_gemm_mxfp8", C.byref(a), C.c_void_p(_p(As)), C.c_void_p(_p(Bs)), _stream(), struct=a, drop=drop)
@@ -286,7 +290,7 @@ def layernorm_fwd(x, gamma, beta, eps, rows, H, *, y_bf16=None, y_f32=None, mean
     a.rows, a.H, a.eps = rows, H, eps
     a.x_rpg, a.x_gstride, a.x_goff = xmap
     a.y_rpg, a.y_gstride, a.y_goff = ymap
-    a.drop_thresh, a.drop_seed, a.drop_stream, a.drop_scale = drop.thresh, drop.seed, drop.stream, drop.scale
+    _set_drop(a, drop)
     a.y_split3 = _h(y_split3)
     a.y_q, a.y_scale = _p(y_q), _p(y_scale)
     _invoke("vault_layernorm_fwd", C.byref(a), _stream(), struct=a, drop=drop)
@@ -304,7 +308,7 @@ def layernorm_bwd(x, mean, rstd, gamma, rows, H, *, dy_bf16=None, dy_f32=None, d
     a.dy_rpg, a.dy_gstride, a.dy_goff = dymap
     a.x_rpg, a.x_gstride, a.x_goff = xmap
     a.dx_rpg, a.dx_gstride, a.dx_goff = dxmap
-    a.drop_thresh, a.drop_seed, a.drop_stream, a.drop_scale = drop.thresh, drop.seed, drop.stream, drop.scale
+    _set_drop(a, drop)
     a.drop_on_dy = 1 if drop_on_dy else 0
     a.dbias = _p(dbias)
     _invoke("vault_layernorm_bwd", C.byref(a), _stream(), struct=a, drop=drop)
@@ -330,7 +334,7 @@ def _attn_args(qkv, keymask, ctx, lse, B, S, H, heads, dctx=None, dqkv=None, dro
     a.ctx_split3 = _h(ctx_split3)
     a.qkv, a.keymask, a.ctx, a.lse, a.dctx, a.dqkv = _h(qkv), _p(keymask), _h(ctx), _p(lse), _h(dctx), _h(dqkv)
     a.B, a.S, a.H, a.heads = B, S, H, heads
-    a.drop_thresh, a.drop_seed, a.drop_stream, a.drop_scale = drop.thresh, drop.seed, drop.stream, drop.scale
+    _set_drop(a, drop)
     return a
 
 
@@ -472,7 +476,7 @@ def _head_args(pre, Wc, bc, labels, pooled, logits, loss_sum, B, H, Cc, loss_sca
     a.pooled, a.logits, a.loss_sum, a.dWc, a.dbc, a.dpre_bf16 = (_p(pooled), _p(logits), _p(loss_sum), _p(dWc),
                                                                  _p(dbc), _p(dpre))
     a.B, a.H, a.C, a.loss_scale, a.grad_scale = B, H, Cc, loss_scale, grad_scale
-    a.drop_thresh, a.drop_seed, a.drop_stream, a.drop_scale = drop.thresh, drop.seed, drop.stream, drop.scale
+    _set_drop(a, drop)
     return a
 
 
