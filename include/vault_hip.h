@@ -346,6 +346,21 @@ int vault_adamw_step_grouped(float* p, float* g, float* m, float* v, void* p_bf1
                              const unsigned char* group_map, const float* group_table, int n_groups, float lr_factor,
                              float beta1, float beta2, float eps, float bias_corr_factor, float grad_scale,
                              const float* coef, int zero_grad, const unsigned char* zero_mask, void* stream);
+/* Exponential moving average (EMA) of the weights, kept beside the flat parameter buffer (the reference keeps a best model
+ * instead: ref vault/tmsc_utils/trainer.py:127-155).  Additions to ABI 12.
+ *   vault_adamw_step_ema: vault_adamw_step_grouped with one more f32 stream `ema` (n elements).  p, g, m, v and p_bf16 come
+ *   out bit-identical to vault_adamw_step_grouped; after an element's update ema <- fmaf(one_minus_decay, p_new - ema, ema)
+ *   in f32 (where p_new == ema the average keeps its bits).  one_minus_decay = 1 - decay, in (0, 1], computed by the caller
+ *   in double precision and rounded once.  Idle elements (g = m = v = 0 in a group without weight decay) keep p, m, v, the
+ *   gradient and the shadow as in vault_adamw_step; an f32x4 of them is skipped altogether only when its four ema equal its
+ *   four p bit for bit, otherwise its ema alone is updated and stored.  42 B per parameter against 34.
+ *   vault_ema_swap: p[i] <-> ema[i] in place for i in [0, n), and p_bf16[i] (may be null) = the 16-bit image of the new
+ *   p[i], in one pass (18 B per parameter).  Two calls restore every bit of the three buffers.  n % 4 == 0, p != ema. */
+int vault_adamw_step_ema(float* p, float* g, float* m, float* v, void* p_bf16, float* ema, long long n,
+                         const unsigned char* group_map, const float* group_table, int n_groups, float lr_factor,
+                         float beta1, float beta2, float eps, float bias_corr_factor, float grad_scale, const float* coef,
+                         float one_minus_decay, int zero_grad, const unsigned char* zero_mask, void* stream);
+int vault_ema_swap(float* p, float* ema, void* p_bf16, long long n, void* stream);
 int vault_cast_bf16(const float* x, void* y_bf16, long long n, void* stream);
 /* Debug census of a 16-bit tensor in the library's operand format (ABI 9; nothing in the reference, which runs fp32:
  * ref vault/tmsc_utils/trainer.py:353-367 has no autocast): out4[0] += elements at the largest finite magnitude (what a

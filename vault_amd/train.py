@@ -19,6 +19,7 @@ trainer.py:369); read ``TrainStep.loss`` when needed.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import re
@@ -107,6 +108,51 @@ def build_param_groups(layout, param_groups: Optional[Sequence[dict]], lr: float
             o, shp = layout.offsets[n]
             gmap[o // 64:(o + int(np.prod(shp)) + 63) // 64] = k + 1      # (every tensor starts 64-aligned)
     return gmap, np.asarray(table, np.float32).reshape(-1, 2)
+
+
+# ---- weight average and optimizer state ------------------------------------------------------------------------------
+def ema_decay_at(decay: float, t: int, warmup: bool = False) -> float:
+    """Decay of the weight average at optimizer step ``t`` (1-based): ``decay``, or with the usual EMA warm-up
+    ``min(decay, (1 + t) / (10 + t))`` - the first steps weigh the fresh weights more, so that the average leaves the
+    initial weights quickly (2 / 11 at t = 1)."""
+    decay = float(decay)
+    return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
+
+
+OPTIMIZER_STATE_KEYS = ("step_idx", "drop_seed", "exp_avg", "exp_avg_sq", "ema", "hyper")
+
+
+def check_optimizer_state(layout, sd, want_ema: bool) -> None:
+    """Check a ``TrainStep.state_dict()`` against a parameter layout (``offsets``, ``trainable``: a ParamStore or
+    ParamStore.layout()) before anything is written.  ``exp_avg``, ``exp_avg_sq`` (and ``ema`` when ``want_ema``) must name
+    every trainable parameter exactly once with its shape: ValueError for a name that is unknown, not trainable or missing,
+    for a tensor of the wrong shape, and for an ``ema`` entry that is there without ``want_ema`` or absent with it.  The
+    ``hyper`` entries are not compared: the receiving step's own values hold."""
+    if not isinstance(sd, dict):
+        raise ValueError("optimizer state must be a dict (TrainStep.state_dict())")
+    lost = [k for k in OPTIMIZER_STATE_KEYS if k not in sd and k != "hyper"]
+    if lost:
+        raise ValueError(f"optimizer state lacks {lost}")
+    if sd["ema"] is not None and not want_ema:
+        raise ValueError("optimizer state carries a weight average, this step keeps none (ema_decay=None)")
+    if sd["ema"] is None and want_ema:
+        raise ValueError("optimizer state carries no weight average, this step keeps one (ema_decay)")
+    trainable = set(layout.trainable)
+    for key in ("exp_avg", "exp_avg_sq") + (("ema",) if want_ema else ()):
+        part = sd[key]
+        if not isinstance(part, dict):
+            raise ValueError(f"optimizer state [{key!r}] must be a dict of tensors by parameter name")
+        for n, t in part.items():
+            if n not in layout.offsets:
+                raise ValueError(f"optimizer state [{key!r}]: unknown parameter {n!r}")
+            if n not in trainable:
+                raise ValueError(f"optimizer state [{key!r}]: {n!r} is not trained by this engine (frozen or without gradient)")
+            if tuple(t.shape) != tuple(layout.offsets[n][1]):
+                raise ValueError(f"optimizer state [{key!r}][{n!r}] has shape {tuple(t.shape)}, the parameter "
+                                 f"{tuple(layout.offsets[n][1])}")
+        missing = [n for n in layout.trainable if n not in part]
+        if missing:
+            raise ValueError(f"optimizer state [{key!r}] lacks {len(missing)} trainable parameter(s), the first: {missing[0]!r}")
 
 
 class GradBuckets:
@@ -507,12 +553,16 @@ class TrainStep:
                  process_group=None, bucket_mb: float = 64.0, constant_lr: bool = False, use_tape: bool = True,
                  assume_full_pixel_mask: bool = False, wire: Optional[str] = None, sparse_embedding: Optional[bool] = None,
                  precise_forward: bool = False, max_grad_norm: Optional[float] = None,
-                 param_groups: Optional[Sequence[dict]] = None, track_grad_norm: bool = False):
+                 param_groups: Optional[Sequence[dict]] = None, track_grad_norm: bool = False,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
         """``max_grad_norm``: clip the global L2 norm of the gradient before AdamW (torch.nn.utils.clip_grad_norm_, HF
         ``TrainingArguments.max_grad_norm``); ``param_groups``: ``[{"params": [names], "lr": .., "weight_decay": ..}, ..]``
         (engine parameter names = state_dict keys; unnamed parameters form the default group at ``learning_rate`` /
         ``weight_decay``; every group follows the schedule from its own base lr); ``track_grad_norm``: keep the norm without
-        clipping.  With either norm option ``grad_norm`` holds the step's pre-clip norm on the device."""
+        clipping.  With either norm option ``grad_norm`` holds the step's pre-clip norm on the device.
+        ``ema_decay`` (0 <= d < 1; None: no average): keep an exponential moving average of the trainable weights in ``ema``,
+        moved inside the optimizer's own pass (``ema <- ema + (1 - d_t)(p - ema)``, d_t = :func:`ema_decay_at` with
+        ``ema_warmup``); :meth:`ema_weights` evaluates or saves the averaged model."""
         self.engine = engine
         self.lr, self.b1, self.b2, self.eps, self.wd = learning_rate, adam_beta1, adam_beta2, adam_epsilon, weight_decay
         if max_grad_norm is not None and not (float(max_grad_norm) > 0.0):
@@ -522,11 +572,23 @@ class TrainStep:
         # the step's gradient norm (0-dim f32 on the device, written by the kernel: no host sync), None without the options
         self.grad_norm: Optional[torch.Tensor] = None
         self._group_map = self._group_table = self._norm_partials = None
-        if param_groups is not None or self.max_grad_norm is not None:
-            # the grouped AdamW (one group when only clipping is asked for: it reads the clip factor from the device)
+        if ema_decay is not None and not (0.0 <= float(ema_decay) < 1.0):
+            raise ValueError("ema_decay must lie in [0, 1) (None: no weight average)")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        # the average of P.p[:n_train] (f32 on the device; frozen parameters lie behind n_train and need none), None without
+        # the option
+        self.ema: Optional[torch.Tensor] = None
+        self._ema_swapped = False      # inside ema_weights(): P.p holds the average, self.ema the trained weights
+        if param_groups is not None or self.max_grad_norm is not None or self.ema_decay is not None:
+            # the grouped AdamW (one group when only clipping or the average is asked for: it reads the clip factor from the
+            # device, and its sibling with the average takes the same group map)
             gmap, table = build_param_groups(engine.params, param_groups, learning_rate, weight_decay)
             self._group_map = torch.from_numpy(gmap).to(engine.device)
             self._group_table = torch.from_numpy(table).to(engine.device)
+        if self.ema_decay is not None:
+            self.ema = torch.empty(engine.params.n_train, dtype=torch.float32, device=engine.device)
+            self.reset_ema()
         if self._needs_norm:
             self._norm_partials = torch.empty(ops.GRAD_NORM_PARTIALS, dtype=torch.float64, device=engine.device)
         self.correct_bias = correct_bias
@@ -606,6 +668,7 @@ class TrainStep:
         """One optimisation step.  The first call for a (B, T) shape runs eagerly and records the call
         tape (ops.Tape); later calls copy the batch into the persistent input buffers and replay it."""
         eng = self.engine
+        self._refuse_inside_ema_weights("a training step")
         B, T = batch["input_ids"].shape
         if self.reducer:
             # (a step that raised inside the exchange never reached finish(): its frontier and its events are dropped here,
@@ -708,6 +771,7 @@ class TrainStep:
         With ``max_grad_norm`` / ``track_grad_norm`` a pass over the whole range first measures the gradient norm (and
         clips); clipping refuses a partial range.  With parameter groups ``lo`` must be 64-aligned."""
         eng = self.engine
+        self._refuse_inside_ema_weights("optimizer_step")
         P = eng.params
         hi = P.n_train if hi is None else hi
         full = lo == 0 and hi == P.n_train
@@ -736,7 +800,14 @@ class TrainStep:
                                   self.max_grad_norm if self.max_grad_norm is not None else math.inf, gscale)
                     self.grad_norm = out[0]
                     coef = out[1:] if self.max_grad_norm is not None else None
-                if self._group_map is not None:
+                if self.ema is not None:
+                    # (both halves of a split pass run at the same t: the counter advances behind the second)
+                    omd = 1.0 - ema_decay_at(self.ema_decay, t, self.ema_warmup)
+                    ops.adamw_step_ema(P.p[lo:hi], P.g[lo:hi], P.m[lo:hi], P.v[lo:hi], P.pb[lo:hi], self.ema[lo:hi], hi - lo,
+                                       self._group_map[lo // 64:(hi + 63) // 64], self._group_table, self.lr_factor(),
+                                       self.b1, self.b2, self.eps, omd, bias_corr_factor=bc, grad_scale=gscale, coef=coef,
+                                       zero_grad=True, zero_mask=None if zm is None else zm[lo // 64:hi // 64])
+                elif self._group_map is not None:
                     ops.adamw_step_grouped(P.p[lo:hi], P.g[lo:hi], P.m[lo:hi], P.v[lo:hi], P.pb[lo:hi], hi - lo,
                                            self._group_map[lo // 64:(hi + 63) // 64], self._group_table, self.lr_factor(),
                                            self.b1, self.b2, self.eps, bias_corr_factor=bc, grad_scale=gscale, coef=coef,
@@ -750,6 +821,83 @@ class TrainStep:
                 P.refresh_transposed()   # W^T shadow of the data-gradient GEMMs, from the bf16 shadow just written
             P._pb3_fresh = False   # the split-bf16 (precise inference) shadow is stale now
             self.step_idx += 1
+
+    # ---- weight average ---------------------------------------------------------------------------------------------
+    def _refuse_inside_ema_weights(self, what: str):
+        if self._ema_swapped:
+            raise RuntimeError(f"{what} inside ema_weights(): the parameter buffer holds the averaged weights")
+
+    def reset_ema(self):
+        """Start the average over from the current weights (for a caller who loaded weights after building the step)."""
+        if self.ema is None:
+            raise RuntimeError("this TrainStep keeps no weight average (ema_decay=None)")
+        self._refuse_inside_ema_weights("reset_ema")
+        self.ema.copy_(self.engine.params.p[:self.engine.params.n_train])
+
+    def _swap_ema(self):
+        eng = self.engine
+        P = eng.params
+        with torch.cuda.device(eng.device), ops.operand_format(eng.half):
+            ops.ema_swap(P.p, self.ema, P.pb, P.n_train)
+            P.refresh_transposed()
+        P._pb3_fresh = False
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the engine runs on the averaged weights: the average and the trainable part of the flat
+        parameter buffer change places ON the device (recorded tapes and the model classes' ``nn.Parameter`` views point
+        into that buffer), with the 16-bit, transposed and split shadows following - ``engine.forward(..., train=False)``,
+        :func:`evaluate`, ``ParamStore.state_dict_numpy()`` and a model's ``state_dict()`` / ``save_pretrained`` all see
+        the average.  Leaving the block, also by an exception, swaps back: every buffer has its old bits again.  Training
+        steps, ``optimizer_step`` and a nested ``ema_weights()`` inside the block raise RuntimeError."""
+        if self.ema is None:
+            raise RuntimeError("this TrainStep keeps no weight average (ema_decay=None)")
+        self._refuse_inside_ema_weights("ema_weights()")
+        self._swap_ema()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swapped = False
+            self._swap_ema()
+
+    # ---- optimizer state --------------------------------------------------------------------------------------------
+    def _named(self, buf: torch.Tensor) -> Dict[str, torch.Tensor]:
+        P = self.engine.params
+        host = buf[:P.n_train].detach().cpu()
+        return {n: P._view(host, n).clone() for n in P.trainable}
+
+    def state_dict(self) -> dict:
+        """What a run needs besides the weights to continue where it stopped, as CPU tensors by parameter name: the AdamW
+        moments (``exp_avg``, ``exp_avg_sq``), the weight average (``ema``, None without one), the step counter (the
+        schedule's position) and the engine's dropout seed; ``hyper`` records the step's settings for the reader.  The
+        weights themselves are saved by the model (``state_dict()`` / ``save_pretrained``), as before.  To resume: load the
+        weights, build the step, then :meth:`load_state_dict`."""
+        self._refuse_inside_ema_weights("state_dict")
+        P = self.engine.params
+        return {"step_idx": int(self.step_idx), "drop_seed": int(self.engine.drop_seed),
+                "exp_avg": self._named(P.m), "exp_avg_sq": self._named(P.v),
+                "ema": None if self.ema is None else self._named(self.ema),
+                "hyper": dict(lr=self.lr, betas=(self.b1, self.b2), eps=self.eps, weight_decay=self.wd,
+                              correct_bias=self.correct_bias, total_steps=self.total_steps, warmup_steps=self.warmup_steps,
+                              ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)}
+
+    def load_state_dict(self, sd: dict):
+        """Write a :meth:`state_dict` into the moments, the average, the step counter and the engine's dropout seed
+        (checked first by :func:`check_optimizer_state`: nothing is written when it raises).  Hyper-parameters are not
+        taken over: this step's own hold."""
+        self._refuse_inside_ema_weights("load_state_dict")
+        P = self.engine.params
+        check_optimizer_state(P, sd, self.ema is not None)
+        for key, buf in (("exp_avg", P.m), ("exp_avg_sq", P.v), ("ema", self.ema)):
+            if buf is None:
+                continue
+            host = buf[:P.n_train].detach().cpu()           # (the padding between tensors keeps what it holds)
+            for n in P.trainable:
+                P._view(host, n).copy_(torch.as_tensor(sd[key][n], dtype=torch.float32))
+            buf[:P.n_train].copy_(host)
+        self.step_idx = int(sd["step_idx"])
+        self.engine.drop_seed = int(sd["drop_seed"]) & 0xFFFFFFFF
 
 
 def evaluation_metrics(eval_true, eval_preds) -> Dict[str, float]:
