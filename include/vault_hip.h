@@ -361,6 +361,26 @@ int vault_adamw_step_ema(float* p, float* g, float* m, float* v, void* p_bf16, f
                          float beta1, float beta2, float eps, float bias_corr_factor, float grad_scale, const float* coef,
                          float one_minus_decay, int zero_grad, const unsigned char* zero_mask, void* stream);
 int vault_ema_swap(float* p, float* ema, void* p_bf16, long long n, void* stream);
+/* torch.optim.AdamW arithmetic (what a current HF Trainer steps by default, "adamw_torch"; the reference's own optimizer,
+ * transformers-4.48 AdamW at ref vault/tmsc_utils/trainer.py:244-254, is vault_adamw_step's form).  Addition to ABI 12.
+ *   vault_adamw_step_torch: groups, lr_factor, coef, grad_scale, zero_grad / zero_mask and the shadow as in
+ *   vault_adamw_step_grouped; ema (may be null: no average) and one_minus_decay as in vault_adamw_step_ema.  Per element, in
+ *   f32, with lr_k = lr_factor x lr of the group and ge = g x (grad_scale x coef):
+ *     p <- p x (1 - lr_k x wd_k)                 (first; skipped when the factor is exactly 1)
+ *     m <- b1 m + (1 - b1) ge,  v <- b2 v + (1 - b2) ge^2
+ *     p <- p - (lr_k x inv_bias_corr1) x (m / (sqrt(v) x inv_sqrt_bias_corr2 + eps))
+ *   inv_bias_corr1 = 1 / (1 - b1^t) and inv_sqrt_bias_corr2 = 1 / sqrt(1 - b2^t), both >= 1, computed by the caller in
+ *   double precision: the bias correction is always on, eps sits outside the corrected root and the weights decay before
+ *   the update - the three places in which torch's form differs from vault_adamw_step's.  1 - beta is taken from the
+ *   shortest decimal that rounds to the f32 beta (0.999f -> 0.001, where 1 - 0.999f is 1.3e-5 off, against corrections
+ *   computed for 0.999).  Idle elements (g = m = v = 0 in
+ *   a group whose decay factor is exactly 1) keep p, m, v, the gradient and the shadow; with an average they are skipped
+ *   only when ema holds p's bits, otherwise ema alone moves.  34 B per parameter, 42 with the average.  p != ema. */
+int vault_adamw_step_torch(float* p, float* g, float* m, float* v, void* p_bf16, float* ema /* NULL: no average */,
+                           long long n, const unsigned char* group_map, const float* group_table, int n_groups,
+                           float lr_factor, float beta1, float beta2, float eps, float inv_bias_corr1,
+                           float inv_sqrt_bias_corr2, float grad_scale, const float* coef, float one_minus_decay,
+                           int zero_grad, const unsigned char* zero_mask, void* stream);
 int vault_cast_bf16(const float* x, void* y_bf16, long long n, void* stream);
 /* Debug census of a 16-bit tensor in the library's operand format (ABI 9; nothing in the reference, which runs fp32:
  * ref vault/tmsc_utils/trainer.py:353-367 has no autocast): out4[0] += elements at the largest finite magnitude (what a

@@ -562,6 +562,27 @@ def adamw_step_ema(p, g, m, v, p_bf16, ema, n, group_map, group_table, lr_factor
             C.c_float(one_minus_decay), C.c_int(1 if zero_grad else 0), C.c_void_p(_p(zero_mask)), _stream())
 
 
+def adamw_step_torch(p, g, m, v, p_bf16, n, group_map, group_table, lr_factor, beta1, beta2, eps, inv_bias_corr1,
+                     inv_sqrt_bias_corr2, ema=None, one_minus_decay=1.0, grad_scale=1.0, coef=None, zero_grad=True,
+                     zero_mask=None):
+    """The grouped AdamW in torch.optim.AdamW's arithmetic (vault_adamw_step_torch): the weights decay before the update,
+    the bias correction is always on (``inv_bias_corr1`` = 1 / (1 - b1^t), ``inv_sqrt_bias_corr2`` = 1 / sqrt(1 - b2^t),
+    computed by the caller in double precision: train.adam_bias_corrections) and eps is added to the corrected root.
+    ``ema`` (optional) and ``one_minus_decay`` as in :func:`adamw_step_ema`, everything else as in
+    :func:`adamw_step_grouped`."""
+    if group_map.dtype != torch.uint8 or group_table.dtype != torch.float32 or group_table.dim() != 2 \
+            or group_table.shape[1] != 2 or group_map.numel() < (n + 63) // 64:
+        raise ValueError("group_map: uint8, one byte per 64 elements; group_table: float32 [n_groups, 2]")
+    if ema is not None and (ema.dtype != torch.float32 or ema.numel() < n):
+        raise ValueError("ema: float32, one element per parameter of the range")
+    _invoke("vault_adamw_step_torch", C.c_void_p(_p(p)), C.c_void_p(_p(g)), C.c_void_p(_p(m)), C.c_void_p(_p(v)),
+            C.c_void_p(_h(p_bf16)), C.c_void_p(_p(ema)), C.c_longlong(n), C.c_void_p(_p(group_map)),
+            C.c_void_p(_p(group_table)), C.c_int(group_table.shape[0]), C.c_float(lr_factor), C.c_float(beta1),
+            C.c_float(beta2), C.c_float(eps), C.c_float(inv_bias_corr1), C.c_float(inv_sqrt_bias_corr2),
+            C.c_float(grad_scale), C.c_void_p(_p(coef)), C.c_float(one_minus_decay), C.c_int(1 if zero_grad else 0),
+            C.c_void_p(_p(zero_mask)), _stream())
+
+
 def ema_swap(p, ema, p_bf16, n):
     """p[i] <-> ema[i] in place over [0, n) and the 16-bit shadow of the new p in the same pass (vault_ema_swap); a second
     call restores every bit of the three buffers."""

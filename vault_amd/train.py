@@ -40,6 +40,34 @@ def linear_schedule(base_lr: float, step: int, warmup_steps: int, total_steps: i
     return base_lr * max(0.0, float(total_steps - step) / float(max(1, total_steps - warmup_steps)))
 
 
+def cosine_schedule(base_lr: float, step: int, warmup_steps: int, total_steps: int) -> float:
+    """lr used by optimizer step number ``step`` (0-based) under get_cosine_schedule_with_warmup (half a cosine period: num_cycles
+    0.5, multiplied in HF's order so that the factors agree to the last bit)."""
+    if step < warmup_steps:
+        return base_lr * float(step) / float(max(1, warmup_steps))
+    progress = float(step - warmup_steps) / float(max(1, total_steps - warmup_steps))
+    return base_lr * max(0.0, 0.5 * (1.0 + math.cos(math.pi * 0.5 * 2.0 * progress)))
+
+
+def constant_with_warmup_schedule(base_lr: float, step: int, warmup_steps: int, total_steps: int) -> float:
+    """lr used by optimizer step number ``step`` (0-based) under get_constant_schedule_with_warmup (``total_steps`` plays no
+    part: the signature is the other schedules')."""
+    if step < warmup_steps:
+        return base_lr * float(step) / float(max(1.0, warmup_steps))
+    return base_lr
+
+
+LR_SCHEDULES = {"linear": linear_schedule, "cosine": cosine_schedule, "constant_with_warmup": constant_with_warmup_schedule}
+OPTIMIZERS = ("hf", "torch")      # transformers-4.48 AdamW (the reference's), torch.optim.AdamW
+
+
+def adam_bias_corrections(beta1: float, beta2: float, t: int) -> Tuple[float, float]:
+    """(1 / (1 - beta1^t), 1 / sqrt(1 - beta2^t)) at optimizer step ``t`` (1-based) in double precision: what
+    torch.optim.AdamW divides its step size and the root of the second moment by (vault_adamw_step_torch takes them as
+    factors)."""
+    return 1.0 / (1.0 - beta1 ** t), 1.0 / math.sqrt(1.0 - beta2 ** t)
+
+
 # ---- parameter groups ------------------------------------------------------------------------------------------------
 # transformers' Trainer.get_decay_parameter_names: no weight decay on parameters whose lower-cased name matches one of these,
 # nor on any parameter of an nn.LayerNorm module
@@ -554,7 +582,8 @@ class TrainStep:
                  assume_full_pixel_mask: bool = False, wire: Optional[str] = None, sparse_embedding: Optional[bool] = None,
                  precise_forward: bool = False, max_grad_norm: Optional[float] = None,
                  param_groups: Optional[Sequence[dict]] = None, track_grad_norm: bool = False,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False, optimizer: str = "hf",
+                 lr_schedule: str = "linear"):
         """``max_grad_norm``: clip the global L2 norm of the gradient before AdamW (torch.nn.utils.clip_grad_norm_, HF
         ``TrainingArguments.max_grad_norm``); ``param_groups``: ``[{"params": [names], "lr": .., "weight_decay": ..}, ..]``
         (engine parameter names = state_dict keys; unnamed parameters form the default group at ``learning_rate`` /
@@ -562,7 +591,18 @@ class TrainStep:
         clipping.  With either norm option ``grad_norm`` holds the step's pre-clip norm on the device.
         ``ema_decay`` (0 <= d < 1; None: no average): keep an exponential moving average of the trainable weights in ``ema``,
         moved inside the optimizer's own pass (``ema <- ema + (1 - d_t)(p - ema)``, d_t = :func:`ema_decay_at` with
-        ``ema_warmup``); :meth:`ema_weights` evaluates or saves the averaged model."""
+        ``ema_warmup``); :meth:`ema_weights` evaluates or saves the averaged model.
+        ``optimizer``: ``"hf"`` (the reference's transformers-4.48 AdamW, ``correct_bias`` its flag) or ``"torch"``, the
+        arithmetic of ``torch.optim.AdamW`` (a current HF ``Trainer``'s ``adamw_torch``): always bias-corrected, eps added to
+        the corrected root, the weights decayed before the update.  ``lr_schedule``: ``"linear"``, ``"cosine"`` or
+        ``"constant_with_warmup"`` (HF ``lr_scheduler_type``; ``constant_lr=True`` overrides it)."""
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, not {optimizer!r}")
+        if optimizer == "torch" and correct_bias:
+            raise ValueError("optimizer='torch' always corrects the bias: correct_bias belongs to optimizer='hf'")
+        if lr_schedule not in LR_SCHEDULES:
+            raise ValueError(f"lr_schedule must be one of {tuple(LR_SCHEDULES)}, not {lr_schedule!r}")
+        self.optimizer, self.lr_schedule = optimizer, lr_schedule
         self.engine = engine
         self.lr, self.b1, self.b2, self.eps, self.wd = learning_rate, adam_beta1, adam_beta2, adam_epsilon, weight_decay
         if max_grad_norm is not None and not (float(max_grad_norm) > 0.0):
@@ -580,9 +620,9 @@ class TrainStep:
         # the option
         self.ema: Optional[torch.Tensor] = None
         self._ema_swapped = False      # inside ema_weights(): P.p holds the average, self.ema the trained weights
-        if param_groups is not None or self.max_grad_norm is not None or self.ema_decay is not None:
+        if param_groups is not None or self.max_grad_norm is not None or self.ema_decay is not None or optimizer == "torch":
             # the grouped AdamW (one group when only clipping or the average is asked for: it reads the clip factor from the
-            # device, and its sibling with the average takes the same group map)
+            # device, and its sibling with the average takes the same group map, as does the torch form)
             gmap, table = build_param_groups(engine.params, param_groups, learning_rate, weight_decay)
             self._group_map = torch.from_numpy(gmap).to(engine.device)
             self._group_table = torch.from_numpy(table).to(engine.device)
@@ -656,13 +696,13 @@ class TrainStep:
     def current_lr(self) -> float:
         if self.constant_lr:
             return self.lr
-        return linear_schedule(self.lr, self.step_idx, self.warmup_steps, self.total_steps)
+        return LR_SCHEDULES[self.lr_schedule](self.lr, self.step_idx, self.warmup_steps, self.total_steps)
 
     def lr_factor(self) -> float:
         """The schedule's multiplier of every group's base lr at the current step (LambdaLR)."""
         if self.constant_lr:
             return 1.0
-        return linear_schedule(1.0, self.step_idx, self.warmup_steps, self.total_steps)
+        return LR_SCHEDULES[self.lr_schedule](1.0, self.step_idx, self.warmup_steps, self.total_steps)
 
     def __call__(self, batch: Dict[str, torch.Tensor], labels: torch.Tensor) -> torch.Tensor:
         """One optimisation step.  The first call for a (B, T) shape runs eagerly and records the call
@@ -764,7 +804,7 @@ class TrainStep:
 
     def optimizer_step(self, lo: int = 0, hi: Optional[int] = None, advance: bool = True,
                        zero_mask: Optional[torch.Tensor] = None):
-        """Fused HF-AdamW over elements [lo, hi) of the flat parameter buffer (default: all trainable ones);
+        """Fused AdamW (``optimizer``) over elements [lo, hi) of the flat parameter buffer (default: all trainable ones);
         ``advance=False`` leaves the step counter alone (first part of a split update).  ``zero_mask`` (one byte per 64
         elements of the WHOLE buffer, 0 = leave the gradient un-zeroed) is the fused step's own: a caller that steps the
         optimizer by hand (gradient accumulation, a manual loop) gets every gradient it read cleared.
@@ -800,7 +840,17 @@ class TrainStep:
                                   self.max_grad_norm if self.max_grad_norm is not None else math.inf, gscale)
                     self.grad_norm = out[0]
                     coef = out[1:] if self.max_grad_norm is not None else None
-                if self.ema is not None:
+                if self.optimizer == "torch":
+                    # (both halves of a split pass run at the same t: the counter advances behind the second)
+                    inv_bc1, inv_sqrt_bc2 = adam_bias_corrections(self.b1, self.b2, t)
+                    omd = 1.0 if self.ema is None else 1.0 - ema_decay_at(self.ema_decay, t, self.ema_warmup)
+                    ops.adamw_step_torch(P.p[lo:hi], P.g[lo:hi], P.m[lo:hi], P.v[lo:hi], P.pb[lo:hi], hi - lo,
+                                         self._group_map[lo // 64:(hi + 63) // 64], self._group_table, self.lr_factor(),
+                                         self.b1, self.b2, self.eps, inv_bc1, inv_sqrt_bc2,
+                                         ema=None if self.ema is None else self.ema[lo:hi], one_minus_decay=omd,
+                                         grad_scale=gscale, coef=coef, zero_grad=True,
+                                         zero_mask=None if zm is None else zm[lo // 64:hi // 64])
+                elif self.ema is not None:
                     # (both halves of a split pass run at the same t: the counter advances behind the second)
                     omd = 1.0 - ema_decay_at(self.ema_decay, t, self.ema_warmup)
                     ops.adamw_step_ema(P.p[lo:hi], P.g[lo:hi], P.m[lo:hi], P.v[lo:hi], P.pb[lo:hi], self.ema[lo:hi], hi - lo,
@@ -880,7 +930,7 @@ class TrainStep:
                 "ema": None if self.ema is None else self._named(self.ema),
                 "hyper": dict(lr=self.lr, betas=(self.b1, self.b2), eps=self.eps, weight_decay=self.wd,
                               correct_bias=self.correct_bias, total_steps=self.total_steps, warmup_steps=self.warmup_steps,
-                              ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)}
+                              ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, optimizer=self.optimizer)}
 
     def load_state_dict(self, sd: dict):
         """Write a :meth:`state_dict` into the moments, the average, the step counter and the engine's dropout seed
