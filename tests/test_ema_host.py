@@ -1,17 +1,12 @@
 """Host side of the train step's weight average and resumable optimizer state: the decay schedule, the validation of a saved
-state against the flat layout, the option's argument check and the C ABI declarations (no GPU)."""
-import os
-import re
-import types
-
+state against the flat layout, and the option's argument check (no GPU; the C ABI declarations: tests/test_optim_groups_host.py)."""
 import pytest
 import torch
 
+from tests.optim_common import _stub_engine
 from vault_amd.params import ParamStore
 from vault_amd.spec import VaultSpec
 from vault_amd.train import TrainStep, check_optimizer_state, ema_decay_at
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_ema_decay_without_warmup_is_constant():
@@ -116,16 +111,5 @@ def test_check_optimizer_state_refuses_lm_names_under_freeze_lm():
 
 @pytest.mark.parametrize("decay", [1.0, -0.1, 1.5, float("nan")])
 def test_ema_decay_outside_the_unit_interval_is_refused(decay):
-    lay = ParamStore.layout(VaultSpec.tiny(3, "roberta"))
     with pytest.raises(ValueError, match="ema_decay"):
-        TrainStep(types.SimpleNamespace(params=lay, device="cpu", spec=None), ema_decay=decay)
-
-
-def test_ema_entry_points_are_declared_and_wrapped():
-    hdr = open(os.path.join(ROOT, "include", "vault_hip.h")).read()
-    for name in ("vault_adamw_step_ema", "vault_ema_swap"):
-        assert re.search(r"\bint\s+%s\s*\(" % name, hdr), name
-    assert re.search(r"vault_adamw_step_ema\(float\* p, float\* g, float\* m, float\* v, void\* p_bf16, float\* ema, long long n,",
-                     hdr)
-    from vault_amd import ops
-    assert callable(ops.adamw_step_ema) and callable(ops.ema_swap)
+        TrainStep(_stub_engine(), ema_decay=decay)

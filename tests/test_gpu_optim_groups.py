@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import vault_oracle as O
+from tests.optim_common import _tiny
 from vault_amd import ops
 from vault_amd.engine import VaultEngine
 from vault_amd.spec import VaultSpec, build_state, synthetic_batch
@@ -161,12 +162,6 @@ def test_one_group_without_clipping_is_bit_identical_to_adamw_step(fmt, wd):
 
 
 # ---- TrainStep ------------------------------------------------------------------------------------------------------
-def _tiny():
-    spec = VaultSpec.tiny(3, "roberta")
-    spec.lm.hidden_dropout_prob = 0.0; spec.lm.attention_probs_dropout_prob = 0.0
-    return spec
-
-
 def _oracle_steps(spec, state, bn, nsteps, lr, wd, no_decay, max_norm):
     """O.vault_loss -> clip_grad_norm_ -> per-group hf_adamw_step; returns per step (loss, pre-clip norm, coef) and the state
     after step 1 (p, m, and the unclipped gradient)."""

@@ -7,47 +7,14 @@ import pytest
 import torch
 
 from tests import test_optim_torch_host as H
+from tests.optim_common import _Recurrence, _batch, _engine, _f32, _tiny
 from vault_amd import ops
-from vault_amd.engine import VaultEngine
-from vault_amd.spec import VaultSpec, build_state, synthetic_batch
 from vault_amd.train import TrainStep, adam_bias_corrections, ema_decay_at, hf_no_decay_groups, linear_schedule
 
 pytestmark = pytest.mark.gpu
 
-U = H.U
 GRID_CAP_N = 8192 * 256 * 4 + 64 * 37      # the grid-stride loop takes a second, ragged trip
 B1, B2, EPS = H.B1, H.B2, H.EPS
-
-
-def _f32(x: float) -> float:
-    return float(np.float32(x))
-
-
-class _Recurrence:
-    """e <- e + (1 - d)(p - e) in float64 over the device's own p after each step, and the bound on the kernel's f32 result:
-    a step rounds the subtraction (|p - e| <= 2 max(|p|, |e|), weighted by 1 - d <= 1), the product and the add - at most
-    4 x 2^-24 x max(|p|, |e|) with the slack of a whole rounding - and carries the earlier error on at weight d <= 1:
-    atol = 4 T 2^-24 max(|p|, |e|) after T steps, the magnitudes taken over all steps so far (tests/test_gpu_ema.py)."""
-
-    def __init__(self, e0: torch.Tensor):
-        self.e = e0.double().clone()
-        self.mag = self.e.abs()
-        self.T = 0
-
-    def step(self, p: torch.Tensor, one_minus_decay: float):
-        p = p.double()
-        self.mag = torch.maximum(self.mag, p.abs())
-        self.e = self.e + one_minus_decay * (p - self.e)
-        self.mag = torch.maximum(self.mag, self.e.abs())
-        self.T += 1
-
-    def check(self, ema: torch.Tensor, what=""):
-        err = (ema.double() - self.e).abs()
-        tol = 4.0 * self.T * U * self.mag
-        over = err > tol
-        worst = float((err / tol.clamp_min(1e-300)).max())
-        print(f"ema vs float64 recurrence {what}: T = {self.T}, max err {float(err.max()):.3e}, max err / bound {worst:.3f}")
-        assert not bool(over.any()), (what, int(over.sum()), worst)
 
 
 def _within(bnd, got, want, what):
@@ -236,21 +203,6 @@ def test_argument_errors():
 
 
 # ---- TrainStep ------------------------------------------------------------------------------------------------------
-def _tiny():
-    spec = VaultSpec.tiny(3, "roberta")
-    spec.lm.hidden_dropout_prob = 0.0; spec.lm.attention_probs_dropout_prob = 0.0
-    return spec
-
-
-def _engine(spec, state=None, half="bf16"):
-    return VaultEngine(spec, "cuda:0", state=build_state(spec, 0) if state is None else state, classifier_dropout=0.0,
-                       half=half)
-
-
-def _batch(spec, seed, B=4):
-    bn = synthetic_batch(spec, B, seed=seed, n_classes=3)
-    return bn, {k: torch.from_numpy(v).cuda() for k, v in bn.items() if k != "labels"}, torch.from_numpy(bn["labels"]).cuda()
-
 
 @pytest.mark.parametrize("ema_decay", [None, 0.9])
 def test_train_step_with_the_torch_optimizer_end_to_end(monkeypatch, ema_decay):

@@ -1,22 +1,17 @@
 """Host side of the train step's gradient clipping and parameter groups: argument checks, the group map built from the flat
-layout, the HF no-decay split, the C ABI declarations (no GPU)."""
+layout, the HF no-decay split, the C ABI declarations of every optimizer entry point (no GPU)."""
 import os
 import re
-import types
 
 import numpy as np
 import pytest
 
+from tests.optim_common import _stub_engine
 from vault_amd.params import ParamStore
 from vault_amd.spec import VaultSpec, param_entries
 from vault_amd.train import TrainStep, build_param_groups, no_decay_parameter_names
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _stub_engine(layout):
-    """What TrainStep reads before it touches a device: the parameter layout (its checks run first)."""
-    return types.SimpleNamespace(params=layout, device="cpu", spec=None)
 
 
 @pytest.mark.parametrize("groups,match", [
@@ -114,10 +109,35 @@ def test_no_decay_names_see_the_mlp_heads_layernorm_by_module():
                                                              "classifier.3.bias"]
 
 
-def test_clip_and_group_entry_points_are_declared():
-    hdr = open(os.path.join(ROOT, "include", "vault_hip.h")).read()
-    for name in ("vault_grad_norm", "vault_adamw_step_grouped"):
-        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), name
-    assert re.search(r"#define\s+VAULT_GRAD_NORM_PARTIALS\s+(\d+)", hdr)
+_TORCH_PARAMS = ["float* p", "float* g", "float* m", "float* v", "void* p_bf16", "float* ema", "long long n",
+                 "const unsigned char* group_map", "const float* group_table", "int n_groups", "float lr_factor",
+                 "float beta1", "float beta2", "float eps", "float inv_bias_corr1", "float inv_sqrt_bias_corr2",
+                 "float grad_scale", "const float* coef", "float one_minus_decay", "int zero_grad",
+                 "const unsigned char* zero_mask", "void* stream"]
+
+
+# (symbol of include/vault_hip.h, its name in ops, the parameters its declaration starts with - all of them for the torch form)
+_DECLARED = [("vault_grad_norm", "grad_norm", None),
+             ("VAULT_GRAD_NORM_PARTIALS", "GRAD_NORM_PARTIALS", None),
+             ("vault_adamw_step_grouped", "adamw_step_grouped", None),
+             ("vault_adamw_step_ema", "adamw_step_ema", _TORCH_PARAMS[:7]),
+             ("vault_ema_swap", "ema_swap", None),
+             ("vault_adamw_step_torch", "adamw_step_torch", _TORCH_PARAMS)]
+
+
+@pytest.mark.parametrize("symbol,wrapper,params", _DECLARED, ids=[d[0] for d in _DECLARED])
+def test_optimizer_entry_points_are_declared_and_wrapped(symbol, wrapper, params):
     from vault_amd import ops
-    assert int(re.search(r"#define\s+VAULT_GRAD_NORM_PARTIALS\s+(\d+)", hdr).group(1)) == ops.GRAD_NORM_PARTIALS
+    hdr = open(os.path.join(ROOT, "include", "vault_hip.h")).read()
+    if symbol.isupper():
+        m = re.search(r"#define\s+" + symbol + r"\s+(\d+)", hdr)
+        assert m and int(m.group(1)) == getattr(ops, wrapper)
+        return
+    assert re.search(r"\bint\s+" + symbol + r"\s*\(", hdr), symbol
+    assert callable(getattr(ops, wrapper))
+    if params is not None:
+        m = re.search(r"\bint\s+" + symbol + r"\s*\((.*?)\)\s*;", hdr, re.S)
+        assert m
+        args = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
+        args = [re.sub(r"\s+", " ", a_).strip() for a_ in args.split(",")]
+        assert args[:len(params)] == params and (params is not _TORCH_PARAMS or args == params)

@@ -1,6 +1,6 @@
 """Host side of the train step's torch.optim.AdamW option: the inputs, the float64 reference (``torch.optim.AdamW`` itself,
 single-tensor, on the CPU) and the error bounds that tests/test_gpu_optim_torch.py holds the kernel to - calibrated here without
-a GPU - plus the option's argument checks, the bias corrections, the warm-up schedules and the C ABI declaration.
+a GPU - plus the option's argument checks, the bias corrections and the warm-up schedules.
 
 The bounds, with u = 2^-24, after t steps, per element i:
   weights  |p - p64| <= t u (4 P_i + 32 S_i): P_i the largest |p_i| of the float64 run so far (the start included) - the roundings
@@ -10,30 +10,20 @@ The bounds, with u = 2^-24, after t steps, per element i:
 The weights and gradients are smaller than the workload's on purpose: that is what puts the eps placement and the decay order
 above ulp(p)."""
 import math
-import os
-import re
 import types
 
 import numpy as np
 import pytest
 import torch
 
-from vault_amd.params import ParamStore
-from vault_amd.spec import VaultSpec
+from tests.optim_common import U, _f32, _stub_engine
 from vault_amd.train import (LR_SCHEDULES, TrainStep, adam_bias_corrections, constant_with_warmup_schedule, cosine_schedule,
                              linear_schedule)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-U = 2.0 ** -24                     # unit roundoff of f32
 GROUPS = [(2e-3, 0.1), (1e-2, 0.0), (5e-3, 0.5)]
 FACTORS = [1.0, 0.75, 0.5, 0.25]
 B1, B2, EPS, T = 0.9, 0.999, 1e-8, 4
 COEF = 0.37                        # the clip factor the kernel reads from the device
-
-
-def _f32(x: float) -> float:
-    return float(np.float32(x))
 
 
 def make_case(n64=210, seed=3, steps=T):
@@ -222,17 +212,13 @@ def test_short_decimal_recovers_the_usual_betas():
 
 
 # ---- options ---------------------------------------------------------------------------------------------------------------
-def _stub():
-    return types.SimpleNamespace(params=ParamStore.layout(VaultSpec.tiny(3, "roberta")), device="cpu", spec=None)
-
-
 def test_option_checks_come_before_any_allocation():
     with pytest.raises(ValueError, match="optimizer"):
-        TrainStep(_stub(), optimizer="adam")
+        TrainStep(_stub_engine(), optimizer="adam")
     with pytest.raises(ValueError, match="correct_bias"):
-        TrainStep(_stub(), optimizer="torch", correct_bias=True)
+        TrainStep(_stub_engine(), optimizer="torch", correct_bias=True)
     with pytest.raises(ValueError, match="lr_schedule"):
-        TrainStep(_stub(), lr_schedule="nope")
+        TrainStep(_stub_engine(), lr_schedule="nope")
     # (an engine without any attribute: the checks ran before the step looked at it)
     for bad in (dict(optimizer="adam"), dict(optimizer="torch", correct_bias=True), dict(lr_schedule="nope")):
         with pytest.raises(ValueError):
@@ -240,11 +226,11 @@ def test_option_checks_come_before_any_allocation():
 
 
 def test_torch_option_builds_one_group_and_default_builds_none():
-    step = TrainStep(_stub(), optimizer="torch", learning_rate=3e-4, weight_decay=0.25)
+    step = TrainStep(_stub_engine(), optimizer="torch", learning_rate=3e-4, weight_decay=0.25)
     assert step.optimizer == "torch" and step._group_map is not None and not step._group_map.any()
     assert step._group_table.tolist() == [[_f32(3e-4), 0.25]]
     assert step.ema is None and step._norm_partials is None
-    plain = TrainStep(_stub())
+    plain = TrainStep(_stub_engine())
     assert plain.optimizer == "hf" and plain.lr_schedule == "linear" and plain._group_map is None
 
 
@@ -283,29 +269,13 @@ def test_schedules_equal_the_transformers_functions(warmup, total):
 def test_train_step_uses_the_chosen_schedule():
     assert LR_SCHEDULES["linear"] is linear_schedule
     for name, fn in LR_SCHEDULES.items():
-        step = TrainStep(_stub(), learning_rate=2e-5, warmup_ratio=0.12, total_steps=25, lr_schedule=name)
+        step = TrainStep(_stub_engine(), learning_rate=2e-5, warmup_ratio=0.12, total_steps=25, lr_schedule=name)
         assert step.warmup_steps == 3
-        flat = TrainStep(_stub(), learning_rate=2e-5, warmup_ratio=0.12, total_steps=25, lr_schedule=name, constant_lr=True)
+        flat = TrainStep(_stub_engine(), learning_rate=2e-5, warmup_ratio=0.12, total_steps=25, lr_schedule=name, constant_lr=True)
         for s in range(30):
             step.step_idx = flat.step_idx = s
             assert step.current_lr() == fn(2e-5, s, 3, 25) and step.lr_factor() == fn(1.0, s, 3, 25)
             assert flat.current_lr() == 2e-5 and flat.lr_factor() == 1.0          # constant_lr wins
-    step = TrainStep(_stub(), learning_rate=2e-5, warmup_ratio=0.12, total_steps=25)
+    step = TrainStep(_stub_engine(), learning_rate=2e-5, warmup_ratio=0.12, total_steps=25)
     step.step_idx = 10
     assert step.current_lr() == linear_schedule(2e-5, 10, 3, 25)                  # the default is today's
-
-
-# ---- declarations ----------------------------------------------------------------------------------------------------------
-def test_torch_entry_point_is_declared_and_wrapped():
-    hdr = open(os.path.join(ROOT, "include", "vault_hip.h")).read()
-    m = re.search(r"\bint\s+vault_adamw_step_torch\s*\((.*?)\)\s*;", hdr, re.S)
-    assert m
-    args = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    args = [re.sub(r"\s+", " ", a).strip() for a in args.split(",")]
-    assert args == ["float* p", "float* g", "float* m", "float* v", "void* p_bf16", "float* ema", "long long n",
-                    "const unsigned char* group_map", "const float* group_table", "int n_groups", "float lr_factor",
-                    "float beta1", "float beta2", "float eps", "float inv_bias_corr1", "float inv_sqrt_bias_corr2",
-                    "float grad_scale", "const float* coef", "float one_minus_decay", "int zero_grad",
-                    "const unsigned char* zero_mask", "void* stream"]
-    from vault_amd import ops
-    assert callable(ops.adamw_step_torch)

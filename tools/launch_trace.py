@@ -19,12 +19,14 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from vault_amd import ops  # noqa: E402
 from vault_amd.engine import VaultEngine  # noqa: E402
 from vault_amd.spec import LMSpec, VaultSpec, ViltSpec, synthetic_batch, synthetic_ragged_batch  # noqa: E402
-from vault_amd.train import TrainStep  # noqa: E402
+from vault_amd.train import TrainStep, hf_no_decay_groups  # noqa: E402
 
 PER_KERNEL = dict(STAGE_MAX_ROWS=0)
 LISTEN = dict(dp_world=2, LM_WGRAD_GROUP=1)
 # name -> engine attributes, then options: `listen` (forward + backward with a stage listener instead of a TrainStep call),
-# `eng` (constructor keywords), `step` (TrainStep keywords), `spec` / `batch` (what runs)
+# `eng` (constructor keywords), `step` (TrainStep keywords), `spec` / `batch` (what runs), `optim` (TrainStep keywords of an
+# optimizer configuration: four un-taped steps under one outer tape, so that the norm pass, the AdamW entry point with every
+# scalar of every step and the shadow refresh are on it; `hf_groups`: param_groups=hf_no_decay_groups(engine))
 CONFIGS = {
     "stage": ({}, {}),
     "per_kernel": (PER_KERNEL, {}),
@@ -38,7 +40,13 @@ CONFIGS = {
     "fp8": ({}, dict(eng=dict(fp8_forward=True))),
     "embeds": ({}, dict(batch="embeds")),
     "full": ({}, dict(spec="full")),
+    "optim_hf": ({}, dict(optim=dict(weight_decay=0.01, correct_bias=True, track_grad_norm=True))),
+    "optim_grouped_clip": ({}, dict(optim=dict(weight_decay=0.01, max_grad_norm=1.0, lr_schedule="cosine"), hf_groups=True)),
+    "optim_ema": ({}, dict(optim=dict(weight_decay=0.01, ema_decay=0.999, ema_warmup=True, correct_bias=True))),
+    "optim_torch": ({}, dict(optim=dict(weight_decay=0.01, optimizer="torch", lr_schedule="constant_with_warmup"))),
+    "optim_torch_ema": ({}, dict(optim=dict(weight_decay=0.01, optimizer="torch", ema_decay=0.99, max_grad_norm=1.0))),
 }
+OPTIM_STEPS = 4
 
 
 def record(name, lm):
@@ -76,6 +84,15 @@ def record(name, lm):
             eng.forward(b, train=True, labels=b["labels"], need_hidden=False)
             eng.zero_grad()
             eng.backward(after_layer=lambda tag: None)
+        finally:
+            ops.stop_tape()
+    elif "optim" in opt:
+        kw = dict(opt["optim"], param_groups=hf_no_decay_groups(eng)) if opt.get("hf_groups") else opt["optim"]
+        step = TrainStep(eng, use_tape=False, total_steps=10, warmup_ratio=0.3, **kw)
+        tape = ops.start_tape()
+        try:
+            for _ in range(OPTIM_STEPS):
+                step(b, b["labels"])
         finally:
             ops.stop_tape()
     else:       # the fused step records its forward + backward itself (between ops.start_tape() and ops.stop_tape())

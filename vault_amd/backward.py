@@ -568,7 +568,7 @@ class BackwardMixin:
 
         def embed_ahead():
             # data-parallel step: the embedding tables' gradient (a third of the bytes on the wire) first, so that its
-            # all-reduce runs under the last group's weight-gradient launches (train.BucketReducer)
+            # all-reduce runs under the last group's weight-gradient launches (exchange.BucketReducer)
             self._lm_embed_backward(ws, d["dy_bf16"], d["dy_f32"])
             embed_done.append(True)
             note("lm_embed")

@@ -1,7 +1,7 @@
 """Host-side driver of the stacked BERT -> ViLT path: owns the flat parameter/gradient buffers and
 the activation workspace in HBM and enqueues the HIP kernels of libvault_hip.so in order.
 
-PyTorch is used for device memory, streams and (in train.py) torch.distributed only; all arithmetic
+PyTorch is used for device memory, streams and (in train.py / exchange.py) torch.distributed only; all arithmetic
 of the path runs in the hand-written kernels.  Mirrors ref: vault/models/vault/model.py:151-218
 (LM -> inputs_embeds -> ViLT) and, for backward, what autograd does for it.
 

@@ -530,14 +530,23 @@ def grad_norm(g, n, partials_f64, out2_f32, max_norm=float("inf"), unscale=1.0):
             C.c_float(max_norm), C.c_float(unscale), _stream())
 
 
+def _check_groups(group_map, group_table, n):
+    if group_map.dtype != torch.uint8 or group_table.dtype != torch.float32 or group_table.dim() != 2 \
+            or group_table.shape[1] != 2 or group_map.numel() < (n + 63) // 64:
+        raise ValueError("group_map: uint8, one byte per 64 elements; group_table: float32 [n_groups, 2]")
+
+
+def _check_ema(ema, n):
+    if ema is not None and (ema.dtype != torch.float32 or ema.numel() < n):
+        raise ValueError("ema: float32, one element per parameter of the range")
+
+
 def adamw_step_grouped(p, g, m, v, p_bf16, n, group_map, group_table, lr_factor, beta1, beta2, eps, bias_corr_factor=1.0,
                        grad_scale=1.0, coef=None, zero_grad=True, zero_mask=None):
     """AdamW with parameter groups (vault_adamw_step_grouped): ``group_map`` uint8, one group index per 64 elements of the
     range; ``group_table`` f32 [n_groups, 2] of (lr, weight_decay) on the device; group k steps at lr_factor x lr_k;
     ``coef``: optional device f32 scalar (the clip factor) multiplying the gradient."""
-    if group_map.dtype != torch.uint8 or group_table.dtype != torch.float32 or group_table.dim() != 2 \
-            or group_table.shape[1] != 2 or group_map.numel() < (n + 63) // 64:
-        raise ValueError("group_map: uint8, one byte per 64 elements; group_table: float32 [n_groups, 2]")
+    _check_groups(group_map, group_table, n)
     _invoke("vault_adamw_step_grouped", C.c_void_p(_p(p)), C.c_void_p(_p(g)), C.c_void_p(_p(m)), C.c_void_p(_p(v)),
             C.c_void_p(_h(p_bf16)), C.c_longlong(n), C.c_void_p(_p(group_map)), C.c_void_p(_p(group_table)),
             C.c_int(group_table.shape[0]), C.c_float(lr_factor), C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
@@ -550,11 +559,8 @@ def adamw_step_ema(p, g, m, v, p_bf16, ema, n, group_map, group_table, lr_factor
     """:func:`adamw_step_grouped` that also moves the weight average (vault_adamw_step_ema): ``ema`` f32, one element per
     parameter of the range, ``ema <- ema + one_minus_decay (p_new - ema)``; ``one_minus_decay`` = 1 - decay in (0, 1],
     computed by the caller in double precision."""
-    if group_map.dtype != torch.uint8 or group_table.dtype != torch.float32 or group_table.dim() != 2 \
-            or group_table.shape[1] != 2 or group_map.numel() < (n + 63) // 64:
-        raise ValueError("group_map: uint8, one byte per 64 elements; group_table: float32 [n_groups, 2]")
-    if ema is not None and (ema.dtype != torch.float32 or ema.numel() < n):
-        raise ValueError("ema: float32, one element per parameter of the range")
+    _check_groups(group_map, group_table, n)
+    _check_ema(ema, n)
     _invoke("vault_adamw_step_ema", C.c_void_p(_p(p)), C.c_void_p(_p(g)), C.c_void_p(_p(m)), C.c_void_p(_p(v)),
             C.c_void_p(_h(p_bf16)), C.c_void_p(_p(ema)), C.c_longlong(n), C.c_void_p(_p(group_map)),
             C.c_void_p(_p(group_table)), C.c_int(group_table.shape[0]), C.c_float(lr_factor), C.c_float(beta1),
@@ -567,14 +573,11 @@ def adamw_step_torch(p, g, m, v, p_bf16, n, group_map, group_table, lr_factor, b
                      zero_mask=None):
     """The grouped AdamW in torch.optim.AdamW's arithmetic (vault_adamw_step_torch): the weights decay before the update,
     the bias correction is always on (``inv_bias_corr1`` = 1 / (1 - b1^t), ``inv_sqrt_bias_corr2`` = 1 / sqrt(1 - b2^t),
-    computed by the caller in double precision: train.adam_bias_corrections) and eps is added to the corrected root.
+    computed by the caller in double precision: optim.adam_bias_corrections) and eps is added to the corrected root.
     ``ema`` (optional) and ``one_minus_decay`` as in :func:`adamw_step_ema`, everything else as in
     :func:`adamw_step_grouped`."""
-    if group_map.dtype != torch.uint8 or group_table.dtype != torch.float32 or group_table.dim() != 2 \
-            or group_table.shape[1] != 2 or group_map.numel() < (n + 63) // 64:
-        raise ValueError("group_map: uint8, one byte per 64 elements; group_table: float32 [n_groups, 2]")
-    if ema is not None and (ema.dtype != torch.float32 or ema.numel() < n):
-        raise ValueError("ema: float32, one element per parameter of the range")
+    _check_groups(group_map, group_table, n)
+    _check_ema(ema, n)
     _invoke("vault_adamw_step_torch", C.c_void_p(_p(p)), C.c_void_p(_p(g)), C.c_void_p(_p(m)), C.c_void_p(_p(v)),
             C.c_void_p(_h(p_bf16)), C.c_void_p(_p(ema)), C.c_longlong(n), C.c_void_p(_p(group_map)),
             C.c_void_p(_p(group_table)), C.c_int(group_table.shape[0]), C.c_float(lr_factor), C.c_float(beta1),
