@@ -212,6 +212,13 @@ typedef struct vault_attn_args {
                        vault_colsum_partials adds the rows up.  S <= 192. */
   int bias_thirds;   /* 1 = the query third only (H sums; the key third is analytically zero and, without attention dropout, the
                        value third is the column sum of dctx: the caller's shortcut), 3 = q | k | v (S <= 64 only) */
+  int q_rows;        /* addition to ABI 12.  0 = every query row is live.  1 = only query row 0 of every (batch, head) item is (the
+                       last encoder layer under a pooler that reads row 0 alone; S <= 192, no ctx_split3): ctx, dctx and the ctx
+                       operand of bwd are COMPACT, [B padded to 256][H] with the item's row at b; of lse only [b][h][0] is written
+                       by fwd and read by bwd; qkv / dqkv keep their full layout.  fwd computes query tile 0 as always and stores
+                       its row 0: bit-identical to row 0 of the full call.  bwd writes all of dqkv: dk / dv of every key, dq of row
+                       0, zeros in the other dq rows - bit-identical to the full call fed a dctx that is zero on the other rows.
+                       bias_partials as in the full call.  Any other value: EINVAL. */
 } vault_attn_args;
 int vault_attention_fwd(const vault_attn_args* args, void* stream);
 int vault_attention_bwd(const vault_attn_args* args, void* stream);
@@ -287,6 +294,9 @@ int vault_rows_add_f32(const float* src, const float* vec, float* out, int rows,
                        void* stream);
 int vault_rows_gather_bwd_f32(const float* dx, float* dsrc, float* dvec, int rows, int H, int rpg, int gstride, int goff,
                               void* stream);
+/* Addition to ABI 12: out[map(r)] = src[r] for `rows` rows of H 16-bit elements (H % 8 == 0), the same row map: the CLS-row
+ * gradient of the pruned last encoder layer, computed compact, placed into the full token-major residual-gradient buffer. */
+int vault_rows_scatter_bf16(const void* src, void* out, int rows, int H, int rpg, int gstride, int goff, void* stream);
 
 /* ---- head + loss ----------------------------------------------------------------------------
  * pooled = tanh(pre) ; logits = dropout(pooled) Wc^T + bc ; loss_sum += loss_scale * sum_b CE_b

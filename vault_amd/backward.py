@@ -42,8 +42,10 @@ class BackwardMixin:
             ops.pycall(lambda: main.wait_event(ev))
             self._wgrad_pending = False
 
-    def _wgrad(self, dy_bf16, x_bf16, wname, bname, Mtok_pad, Nout, Kin, m_valid, out_rows=0):
+    def _wgrad(self, dy_bf16, x_bf16, wname, bname, Mtok_pad, Nout, Kin, m_valid, out_rows=0, unsplit=False):
         # dW[Nout,Kin] += dY[Mtok,Nout]^T . X[Mtok,Kin] ; db[Nout] += colsum(dY)
+        # (``unsplit``: one pass over the tokens per tile - each element receives ONE float add, so the result does not depend on
+        #  the order of atomics: the 256-token contractions of the pruned last ViLT layer, four k-steps long)
         P = self.params
         gw = P.gr(wname, n_elems=Nout * Kin, shape=(Nout, Kin))
         if gw is None:
@@ -68,6 +70,8 @@ class BackwardMixin:
             tiles = (Nout // 128) * (Kin // 128)
             splits = max(1, min(nk, (self.WGRAD_TARGET_WGS + tiles - 1) // tiles))
             cfg = 0
+        if unsplit:
+            splits = 1
         if cfg == 3:
             ops.pycall(lambda: self._prof_begin("wgrad"))
         ops.gemm(dy_bf16, x_bf16, gw, Nout, Kin, Mtok_pad, Nout, Kin, Kin, 1, 1, ops.EPI_F32_ATOMIC, cfg=cfg,
@@ -136,29 +140,32 @@ class BackwardMixin:
         g = self.LM_WGRAD_GROUP
         return g if g > 0 else n_layers
 
-    def _wgrad_group(self, kinds, layers, i0, hi, Mtok_pad, m_valid):
+    def _wgrad_group(self, kinds, layers, i0, hi, Mtok_pad, m_valid, counts=None):
         """Weight gradients of layers i0 .. hi - 1 of a stack.  ``kinds``: (dY stack, X stack, weight attribute, Nout, Kin) per
         Linear kind.  Every 256 x 256 tile of every kind costs the same (the contraction runs over the tokens), so the tiles
         of all kinds are packed into launches of exactly 256 items - one per CU, un-split, stored (or added) once - and one
         remainder launch whose split count comes from the cost model (vault_wgrad_grouped); one launch per kind leaves 16 %
         of the CUs idle in the 216-tile FFN launches and splits the attention-out / QKV ones 4 / 3 ways with float atomics.
-        Falls back to one batched launch per kind when a shape is not a multiple of 256 (the tiny test models)."""
+        Falls back to one batched launch per kind when a shape is not a multiple of 256 (the tiny test models).
+        ``counts``: layers per kind, i0 .. i0 + count - 1 (default: all of the group; the pruned last ViLT layer contracts its
+        FFN and attention-out gradients itself, over its compact rows: those kinds end one layer earlier)."""
         P = self.params
-        G = hi - i0
+        Gs = [hi - i0] * len(kinds) if counts is None else list(counts)
+        kinds, Gs = [k for k, n in zip(kinds, Gs) if n > 0], [n for n in Gs if n > 0]
         hms = [k[5] if len(k) > 5 else 0 for k in kinds]        # rows per plane of a head-major dY (the QKV kind's dqkv), 0 = row-major
         kinds = [k[:5] for k in kinds]
         ok = all(no % 256 == 0 and ki % 256 == 0 for *_, no, ki in kinds)
         strides = []
-        for dY_all, X_all, wsel, Nout, Kin in kinds:
-            offs = [P.offsets[getattr(l_, wsel)][0] for l_ in layers[i0:hi]]
+        for (dY_all, X_all, wsel, Nout, Kin), G in zip(kinds, Gs):
+            offs = [P.offsets[getattr(l_, wsel)][0] for l_ in layers[i0:i0 + G]]
             so = (offs[1] - offs[0]) if G > 1 else 0
             ok = ok and all(offs[k + 1] - offs[k] == so for k in range(G - 1))
             strides.append(so)
         if not ok:
             if any(hms):
                 raise RuntimeError("head-major dqkv needs the grouped ring weight-gradient launches (_plan_head_major)")
-            for dY_all, X_all, wsel, Nout, Kin in kinds:
-                self._wgrad_batched(dY_all, X_all, [getattr(l_, wsel) for l_ in layers[i0:hi]], i0, Mtok_pad, Nout, Kin, m_valid)
+            for (dY_all, X_all, wsel, Nout, Kin), G in zip(kinds, Gs):
+                self._wgrad_batched(dY_all, X_all, [getattr(l_, wsel) for l_ in layers[i0:i0 + G]], i0, Mtok_pad, Nout, Kin, m_valid)
             return
         nk = Mtok_pad // 64
         # items per launch: one per CU; beside a backward chain on another stream (small batches) fewer, so that the chain's
@@ -167,7 +174,7 @@ class BackwardMixin:
         # items of every kind in list order, cut into launches of CU items (<= 3 segments each)
         remaining = []
         for k, (dY_all, X_all, wsel, Nout, Kin) in enumerate(kinds):
-            remaining.append([k, 0, (Nout // 256) * (Kin // 256) * G])      # kind, first item, items left
+            remaining.append([k, 0, (Nout // 256) * (Kin // 256) * Gs[k]])      # kind, first item, items left
         launches, cur, room = [], [], CU
         for k, first, left in remaining:
             while left > 0:
@@ -196,7 +203,7 @@ class BackwardMixin:
                     for it in range(first, first + c):       # items are (layer-major, tile-minor)
                         covered[(k, it // tpl)] = covered.get((k, it // tpl), 0) + 1
                 gw = P.gr(getattr(layers[i0], wsel), n_elems=Nout * Kin, shape=(Nout, Kin))
-                args.append(dict(dy=dY_all[i0], x=X_all[i0], dw=gw, n_out=Nout, n_in=Kin, batch=G, first=first, count=c,
+                args.append(dict(dy=dY_all[i0], x=X_all[i0], dw=gw, n_out=Nout, n_in=Kin, batch=Gs[k], first=first, count=c,
                                  batch_dy=dY_all.stride(0), batch_x=X_all.stride(0), batch_dw=strides[k], dy_hm=hms[k]))
             ops.pycall(lambda: self._prof_begin("wgrad", st))
             ops.wgrad_grouped(args, Mtok_pad, splits=splits, accumulate=acc)
@@ -298,6 +305,9 @@ class BackwardMixin:
         ws = self.last if ws is None else ws
         if ws is None or not ws.get("train"):
             raise RuntimeError("backward() needs a preceding forward(train=True)")
+        if ws.get("pruned_last") and dhidden is not None:
+            raise ValueError("the forward pruned the last layer to the pooler's rows: a gradient of last_hidden_state needs "
+                             "forward(need_hidden=True)")
         self.drop_seed = ws["drop_seed"]
         note = (lambda tag: ops.pycall(lambda: after_layer(tag))) if after_layer is not None else (lambda tag: None)
         # deferred weight gradients beside the backward chain when its GEMMs are single partial rounds of tiles (same-box
@@ -322,8 +332,10 @@ class BackwardMixin:
         H, FF = ws["H"], ws["FF"]
         kinds = tuple((dy, ws[x], wsel, no, ki) for dy, x, (wsel, no, ki) in
                       zip(dY, X, (("fw", H, FF), ("iw", FF, H), ("ow", H, H), ("qw", 3 * H, H))))
-        return dict(layers=layers, size=self._wgrad_group_size(len(layers), after_layer, tag), kinds=kinds, H=H,
-                    rows_pad=rows_pad, rows=rows)
+        # (``ends``: one past the last layer of each kind; a pruned last ViLT layer keeps only its QKV kind in the groups)
+        n, cut = len(layers), 1 if (tag == "vilt" and ws.get("pruned_last")) else 0
+        return dict(layers=layers, size=self._wgrad_group_size(n, after_layer, tag), kinds=kinds, H=H,
+                    rows_pad=rows_pad, rows=rows, ends=(n - cut, n - cut, n - cut, n))
 
     def _layer_done(self, tag, grp, i, note, after_layer, N=None, hm=0, parts=None, items=0, ahead=None):
         """Layer ``i`` of a stack has run its data gradients: report it (per-layer weight gradients: ``grp`` None) or, at the bottom
@@ -340,7 +352,8 @@ class BackwardMixin:
 
         def launch():
             self._qkv_bias_grads_batched(kinds[3][0], layers, i, hi, 3 * H, grp["rows"], 3 * H if N is None else N, hm=hm, parts=parts)
-            self._wgrad_group(kinds[:3] + (kinds[3] + (hm,),), layers, i, hi, grp["rows_pad"], grp["rows"])
+            self._wgrad_group(kinds[:3] + (kinds[3] + (hm,),), layers, i, hi, grp["rows_pad"], grp["rows"],
+                              counts=[max(0, min(hi, e) - i) for e in grp["ends"]])
         self._wgrads_aside(launch, after_layer, items=items)
         for j in reversed(range(i, hi)):
             note(f"{tag}{j}")
@@ -350,7 +363,11 @@ class BackwardMixin:
         """Classifier / pooler / final LayerNorm: the gradient at the top of the ViLT stack into ``dxb_top``."""
         spec, P, x, nv = self.spec, self.params, ws["x"], len(self.vl)
         B, S, M, H = (ws[k] for k in ("B", "S", "M", "H"))
-        ops.pycall(dxb_top.zero_)
+        # (pruned last layer: the stack's output and the gradient at its top are compact, one row per sample - nothing to clear)
+        pruned = bool(ws.get("pruned_last"))
+        cls_map = (0, 0, 0) if pruned else (1, S, 0)
+        if not pruned:
+            ops.pycall(dxb_top.zero_)
         if spec.add_pooling_layer and (spec.n_classes > 0 or dpooled is not None):
             Bp = ws["Bp"]
             dpre = self._buf(ws, "dpre", (Bp, H), self.hdt)
@@ -371,9 +388,9 @@ class BackwardMixin:
             self._wgrad(dpre, ws["h0b"], "pooler.dense.weight", "pooler.dense.bias", Bp, H, H, B)
             dh0 = self._buf(ws, "dh0", (Bp, H), self.hdt)
             self._dgrad(dpre, "pooler.dense.weight", dh0, Bp, H, H, ops.EPI_BF16, B)
-            ops.layernorm_bwd(x[nv], ws["f_mean"], ws["f_rstd"], P.w("layernorm.weight"), B, H, dy_bf16=dh0,
-                              dx_bf16=dxb_top, dgamma=P.gr("layernorm.weight"),
-                              dbeta=P.gr("layernorm.bias"), xmap=(1, S, 0), dxmap=(1, S, 0),
+            ops.layernorm_bwd(ws["pl_xout"] if pruned else x[nv], ws["f_mean"], ws["f_rstd"], P.w("layernorm.weight"), B, H,
+                              dy_bf16=dh0, dx_bf16=dxb_top, dgamma=P.gr("layernorm.weight"),
+                              dbeta=P.gr("layernorm.bias"), xmap=cls_map, dxmap=cls_map,
                               dbias=None if dhidden is not None else P.gr(self.vl[nv - 1].fb))
         if dhidden is not None:
             # gradient w.r.t. last_hidden_state (all rows): LN backward over all rows, added on top
@@ -417,6 +434,8 @@ class BackwardMixin:
             vb["grp"] = self._wgrad_groups(ws, "vilt", self.vl, after_layer, vb["dY"],
                                            ("act_all", "n2_all", "ctx_all", "n1_all"), Mp, ws["M"])
         vb["top"] = vb["dY"][0][nv - 1] if vb["grp"] else vb["dxb"][0]
+        if ws.get("pruned_last"):
+            vb["top"] = self._buf(ws, "pl_dtop", (ws["Bp"], H), bf)
         return vb
 
     def _backward_vilt_stack(self, ws, vb, after_layer, note):
@@ -448,6 +467,8 @@ class BackwardMixin:
             d["dx_f32"] = vb["dx"] if i == 0 else None
             if staged:
                 self._layer_bwd_staged(ws, "vilt", self.vl, i, d, bool(grp))
+            elif i == nv - 1 and ws.get("pruned_last"):
+                self._vilt_last_layer_bwd_pruned(ws, i, d, bool(grp), short, vparts, vb["top"])
             else:
                 self._vilt_layer_bwd(ws, i, d, bool(grp), short, vparts)
             self._layer_done("vilt", grp, i, note, after_layer, H if short else 3 * H, ws.get("qkv_hm", 0), vparts, beside)
@@ -485,6 +506,43 @@ class BackwardMixin:
         wgrad(dqkv, g("n1"), ln.qw, ln.qb, Mp, 3 * H, H, M)
         # (deferred: the QKV bias gradient's query third - or, without the shortcut, all of it - with the group's launches)
         ops.layernorm_bwd(ws["x"][i], g("m1"), g("r1"), P.w(ln.ln1w), M, H, dy_bf16=dN, dres_bf16=dyB,
+                          dx_f32=d["dx_f32"], dx_bf16=d["dx_bf16"], dgamma=P.gr(ln.ln1w), dbeta=P.gr(ln.ln1b),
+                          dbias=P.gr(self.vl[i - 1].fb) if i > 0 else None)
+
+    def _vilt_last_layer_bwd_pruned(self, ws, i, d, deferred, short, vparts, dtop):
+        """Backward of the last ViLT layer after a pruned forward (engine._vilt_last_layer_pruned): the gradient at the top of
+        the stack is non-zero on the CLS rows only, ``dtop`` holds them compact.  The FFN, LayerNorm 2 and attention-out data
+        gradients run on those Bp rows, and the three weight gradients are Bp-token contractions, launched here, un-split (one
+        add per element into memory the optimizer zeroed - as reproducible as the stored tiles of the grouped launches;
+        _stored_ranges does not list them).  Attention backward has one live query
+        per item and writes all of dqkv; the QKV data gradient, LayerNorm 1 backward and - deferred or not - the QKV weight
+        gradient and bias sums are the full-size layer's.  LayerNorm 1's residual gradient is a full-size buffer that only
+        ever holds the CLS rows (``pl_dres``: zero elsewhere from its allocation)."""
+        P, ln, vhm = self.params, self.vl[i], ws.get("qkv_hm", 0)
+        B, S, M, Mp, H, FF, heads, Bp = (ws[k] for k in ("B", "S", "M", "Mp", "H", "FF", "heads", "Bp"))
+        bf = self.hdt
+        g, c = (lambda k: ws[f"{k}{i}"]), (lambda k: ws[f"pl_{k}"])  # noqa: E731
+        dU, dNc, dmid, dctx = (self._buf(ws, f"pl_{k}", (Bp, w), bf) for k, w in (("dU", FF), ("dN", H), ("dmid", H), ("dctx", H)))
+        dres, dqkv, dN = self._buf(ws, "pl_dres", (Mp, H), bf), d["dqkv"], d["dN"]
+        g8 = ws.get("pl_gelu8")
+        g8kw = dict(cfg=g8, aux_u8=True) if g8 is not None else {}
+        self._dgrad(dtop, ln.fw, dU, Bp, FF, H, ops.EPI_BF16_DGELU, B, aux=c("u"), colsum=P.gr(ln.ib), like=Mp, **g8kw)
+        self._wgrad(dtop, c("act"), ln.fw, None, Bp, H, FF, B, unsplit=True)
+        self._dgrad(dU, ln.iw, dNc, Bp, H, FF, ops.EPI_BF16, B, like=Mp)
+        self._wgrad(dU, c("n2"), ln.iw, None, Bp, FF, H, B, unsplit=True)
+        ops.layernorm_bwd(c("xm"), c("m2"), c("r2"), P.w(ln.ln2w), B, H, dy_bf16=dNc, dres_bf16=dtop, dx_bf16=dmid,
+                          dgamma=P.gr(ln.ln2w), dbeta=P.gr(ln.ln2b), dbias=P.gr(ln.ob))
+        ops.rows_scatter_h16(dmid, dres, B, H, 1, S, 0)          # dres[b S] = dmid[b]
+        # (the value-bias shortcut holds: the only queries with dO != 0 are the CLS rows, and softmax rows still sum to one)
+        gqb = P.gr(ln.qb, n_elems=3 * H, shape=(3 * H,))
+        self._dgrad(dmid, ln.ow, dctx, Bp, H, H, ops.EPI_BF16, B, like=Mp, **(dict(colsum=gqb[2 * H:]) if short else {}))
+        self._wgrad(dmid, c("ctx"), ln.ow, None, Bp, H, H, B, unsplit=True)
+        ops.attention_bwd(g("qkv"), ws["keymask"], c("ctx"), g("lse"), dctx, dqkv, B, S, H, heads, qkv_hm=vhm, q_rows=1,
+                          **(dict(bias_partials=vparts[0][i], bias_thirds=1) if vparts else {}))
+        self._dgrad(dqkv, ln.qw, dN, Mp, H, 3 * H, ops.EPI_BF16, M, **(dict(a_hm=vhm) if vhm else {}))
+        if not deferred:
+            self._wgrad(dqkv, g("n1"), ln.qw, ln.qb, Mp, 3 * H, H, M)
+        ops.layernorm_bwd(ws["x"][i], g("m1"), g("r1"), P.w(ln.ln1w), M, H, dy_bf16=dN, dres_bf16=dres,
                           dx_f32=d["dx_f32"], dx_bf16=d["dx_bf16"], dgamma=P.gr(ln.ln1w), dbeta=P.gr(ln.ln1b),
                           dbias=P.gr(self.vl[i - 1].fb) if i > 0 else None)
 

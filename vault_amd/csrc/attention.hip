@@ -149,7 +149,10 @@ struct AttnDrop {
   float scale;
 };
 
-template <int NKT, int NWV, int WPE, bool DROP = true>
+// Q1 (vault_attn_args.q_rows = 1): only query tile 0 of the item is computed - by the instruction sequence every tile takes - and
+// only its row 0 leaves the kernel: ctx is compact, [B][H] (row b), and lse[b][h][0] alone is written.  Launched with ONE wave
+// per workgroup (the wave stages K and V itself and has the item's only tile): no wave idles through an item.
+template <int NKT, int NWV, int WPE, bool DROP = true, bool Q1 = false>
 __global__ __launch_bounds__(NWV * 64, WPE) void attn_fwd_kernel(const h16* __restrict__ qkv, const float* __restrict__ keymask,
                                                        h16* __restrict__ ctx, float* __restrict__ lse, int S, int H,
                                                        int heads, float scale, AttnDrop dr, h16* __restrict__ ctx3, int hm_rows) {
@@ -180,7 +183,7 @@ __global__ __launch_bounds__(NWV * 64, WPE) void attn_fwd_kernel(const h16* __re
     mb[k] = (k < S && (keymask == nullptr || keymask[(size_t)b * S + k] != 0.f)) ? 0.f : -INFINITY;
   __syncthreads();
   const float sl2 = scale * LOG2E;
-  const int nqt = (S + 15) >> 4;
+  const int nqt = Q1 ? 1 : (S + 15) >> 4;
   const uint32_t bh = (uint32_t)(b * heads + h);
   for (int qt = wave; qt < nqt; qt += NWV) {
     if (qt != wave) {
@@ -245,8 +248,8 @@ __global__ __launch_bounds__(NWV * 64, WPE) void attn_fwd_kernel(const h16* __re
     sum += __shfl_xor(sum, 32, 64);
     const float inv = 1.0f / sum;       // this lane's query row (l15)
 #if ATTN_FWD_WL
-    if (q_l < S && g == 0) lse[(size_t)bh * S + q_l] = mx * scale + __logf(sum);
-    if (ctx3 != nullptr) {   // precise path: [hi | lo | hi] operand of the split-bf16 projection GEMM (16-byte pieces)
+    if ((Q1 ? q_l == 0 : q_l < S) && g == 0) lse[(size_t)bh * S + q_l] = mx * scale + __logf(sum);
+    if (!Q1 && ctx3 != nullptr) {   // precise path: [hi | lo | hi] operand of the split-bf16 projection GEMM (16-byte pieces)
       if (q_l < S) {
         h16* dst = ctx3 + (row0 + q_l) * 3 * H + h * 64 + 8 * g;
 #pragma unroll
@@ -284,11 +287,16 @@ __global__ __launch_bounds__(NWV * 64, WPE) void attn_fwd_kernel(const h16* __re
         wb[k] = lo8 ? xr : w[1][k];
       }
       const int ra = qt * 16 + (l15 & 7);
-      h16* dst = ctx + (row0 + ra) * H + h * 64 + (l15 >> 3) * 32 + 8 * g;
-      if (ra < S) *reinterpret_cast<u32x4*>(dst) = wa;
-      if (ra + 8 < S) *reinterpret_cast<u32x4*>(dst + 8 * (size_t)H) = wb;
+      if (Q1) {   // row 0 alone (its two 64-byte halves: lanes l15 = 0 and 8), into row b of the compact ctx
+        if (ra == 0) *reinterpret_cast<u32x4*>(ctx + (size_t)b * H + h * 64 + (l15 >> 3) * 32 + 8 * g) = wa;
+      } else {
+        h16* dst = ctx + (row0 + ra) * H + h * 64 + (l15 >> 3) * 32 + 8 * g;
+        if (ra < S) *reinterpret_cast<u32x4*>(dst) = wa;
+        if (ra + 8 < S) *reinterpret_cast<u32x4*>(dst + 8 * (size_t)H) = wb;
+      }
     }
 #else
+    static_assert(!Q1, "the one-query form stores whole lines: build it with ATTN_FWD_WL");
     if (q_l < S) {
       if (g == 0) lse[(size_t)bh * S + q_l] = mx * scale + __logf(sum);
       if (ctx3 != nullptr) {   // precise path: [hi | lo | hi] operand of the split-bf16 projection GEMM
@@ -592,7 +600,13 @@ __device__ __forceinline__ void attn_wait_vm() {
 // memory pipeline): every wave reads ALL of Q and dO (row fragments for S^T / dP, transposed ones for dV / dK) whatever keys it
 // owns - 12 waves of one tile read them 12 times, 6 waves of two tiles 6 times, each fragment feeding two MFMAs from registers.
 // Every output element is computed by the same sequence of operations as with KT = 1 (bit-identical dq / dk / dv).
-template <int NKT, int NWV, bool DROP = true, int WPE = 1, int KT = 1>
+// Q1 (vault_attn_args.q_rows = 1): dO is zero except on query row 0 of every item, and ctx / dctx are compact, [B][H] (row b).
+// What the full kernel computes from such a dO, with the arithmetic on exact zeros left out: the dO image is row 0 + zeros, the
+// row statistics of the other queries are (-inf, 0) - their P and dS are exactly 0, as the products with dO = 0 are in the full
+// kernel -, phase 1 runs its first 32-query step only (the others add zeros to dK / dV), phase 2 runs in the wave that owns query
+// tile 0 and the other waves store zeros.  Loads and stores per wave are those of the full kernel (the counted waits hold); the Q
+// rows >= 32, which nothing reads, are requested as row 31 again (cache hits).
+template <int NKT, int NWV, bool DROP = true, int WPE = 1, int KT = 1, bool Q1 = false>
 __global__ __launch_bounds__(NWV * 64, WPE) void attn_bwd_one_kernel(const h16* __restrict__ qkv, const float* __restrict__ keymask,
                                                          const h16* __restrict__ ctx, const h16* __restrict__ dctx,
                                                          const float* __restrict__ lse, h16* __restrict__ dqkv, int S,
@@ -647,9 +661,9 @@ __global__ __launch_bounds__(NWV * 64, WPE) void attn_bwd_one_kernel(const h16* 
   uint32_t off_q[NC], off_o[NC];
 #pragma unroll
   for (int i = 0; i < NC; ++i) {
-    const int c = tid + i * NT, row = min(c >> 3, S - 1), pos = c & 7;
+    const int c = tid + i * NT, row = min(min(c >> 3, S - 1), Q1 ? 31 : SK), pos = c & 7;
     off_q[i] = (uint32_t)row * (uint32_t)(ld * 2) + (uint32_t)pos * 16u;
-    off_o[i] = (uint32_t)row * (uint32_t)(H * 2) + (uint32_t)pos * 16u;
+    off_o[i] = (Q1 ? 0u : (uint32_t)row * (uint32_t)(H * 2)) + (uint32_t)pos * 16u;
   }
   uint32_t off_frag[KT];           // own key rows, d = 8 g (+ 32 s)
 #pragma unroll
@@ -690,8 +704,9 @@ __global__ __launch_bounds__(NWV * 64, WPE) void attn_bwd_one_kernel(const h16* 
     item_bh(item, b, h);
     const size_t row0 = (size_t)b * S;
     const char* qb = attn_uniform(qkv + row0 * ld + (size_t)h * lay.hs);
-    const char* ob = attn_uniform(ctx + row0 * H + h * 64);
-    const char* db = attn_uniform(dctx + row0 * H + h * 64);
+    const size_t orow = Q1 ? (size_t)b : row0;
+    const char* ob = attn_uniform(ctx + orow * H + h * 64);
+    const char* db = attn_uniform(dctx + orow * H + h * 64);
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
       attn_gload16(rq[i], qb, off_q[i]);
@@ -736,6 +751,7 @@ __global__ __launch_bounds__(NWV * 64, WPE) void attn_bwd_one_kernel(const h16* 
     for (int i = 0; i < NC; ++i) {
       const int c = tid + i * NT, row = c >> 3, pos = c & 7;
       const int off = row * 128 + ((pos ^ (swz_row(row) << 1)) << 4);
+      if (Q1 && row != 0) rd[i] = u32x4{0u, 0u, 0u, 0u};      // (every chunk was loaded from the item's one dO row)
       *reinterpret_cast<u32x4*>(Qs + off) = rq[i];
       *reinterpret_cast<u32x4*>(Ds + off) = rd[i];
       float s = 0.f;
@@ -751,7 +767,7 @@ __global__ __launch_bounds__(NWV * 64, WPE) void attn_bwd_one_kernel(const h16* 
     }
     if (tid < SK) {
       mb[tid] = (tid < S && (keymask == nullptr || rm != 0.f)) ? 0.f : -INFINITY;
-      lse_s[tid] = (tid < S) ? -rl * LOG2E : -INFINITY;
+      lse_s[tid] = (Q1 ? tid == 0 : tid < S) ? -rl * LOG2E : -INFINITY;      // (Q1: lse[b][h][0] is all the forward wrote)
     }
   };
 
@@ -802,7 +818,7 @@ __global__ __launch_bounds__(NWV * 64, WPE) void attn_bwd_one_kernel(const h16* 
     {
       char* dsrow = dSs + (tile0 * 16 + l15) * DS_LD + 8 * g;      // tile kt: + 16 kt DS_LD
 _Pragma(ATTN_STR(unroll ATTN_P1_UNROLL))
-      for (int T = 0; T < ((ATTN_ABLATE == 1 || ATTN_ABLATE == 4) ? 0 : NKT); ++T) {
+      for (int T = 0; T < ((ATTN_ABLATE == 1 || ATTN_ABLATE == 4) ? 0 : (Q1 ? 1 : NKT)); ++T) {
         f32x4 p2[KT][2], ds2[KT][2];
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
@@ -928,6 +944,7 @@ _Pragma(ATTN_STR(unroll ATTN_P1_UNROLL))
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) o[kt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
       const char* dsb = dSs + (4 * g + (l15 >> 2)) * DS_LD + tile0 * 32 + (l15 & 3) * 8;     // query tile kt: + 32 kt
+      if (!Q1 || tile0 == 0)      // (Q1: dS is zero beyond query row 0 - the other waves' dQ tiles are zeros)
 #pragma unroll
       for (int T = 0; T < ((ATTN_ABLATE == 1 || ATTN_ABLATE == 3) ? 0 : NKT); ++T) {
         const char* a = dsb + T * 32 * DS_LD;
@@ -1011,10 +1028,25 @@ extern "C" int vault_attention_fwd(const vault_attn_args* a, void* stream) {
     return VAULT_EINVAL;
   if (a->S > 320) return VAULT_EINVAL;
   if (a->qkv_hm != 0 && (a->qkv_hm < a->B * a->S || a->ctx_split3 != nullptr)) return VAULT_EINVAL;
+  // one live query per item: the resident forms (S <= 192) with the compact ctx, not the split3 (precise) output
+  if (a->q_rows != 0 && (a->q_rows != 1 || a->S > 192 || !a->ctx || a->ctx_split3 != nullptr)) return VAULT_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const AttnDrop dr{a->drop_thresh, a->drop_seed, a->drop_stream, a->drop_scale};
   dim3 grid(a->heads, a->B), block(256);
   const float scale = 0.125f;  // 1/sqrt(64)
+#define FWD_Q1(NK, WP, DR)                                                                                             \
+    hipLaunchKernelGGL((attn_fwd_kernel<NK, 1, WP, DR, true>), grid, dim3(64), attn_lds_bytes<NK>(), st,                \
+                       reinterpret_cast<const h16*>(a->qkv), a->keymask, reinterpret_cast<h16*>(a->ctx), a->lse, a->S, \
+                       a->H, a->heads, scale, dr, static_cast<h16*>(nullptr), a->qkv_hm)
+  if (a->q_rows == 1) {   // one wave per workgroup; 17 / 50 KiB of LDS: nine / three workgroups per CU
+    if (a->S <= 64) {
+      if (a->drop_thresh != 0u) FWD_Q1(2, 2, true); else FWD_Q1(2, 2, false);
+    } else {
+      if (a->drop_thresh != 0u) FWD_Q1(6, 1, true); else FWD_Q1(6, 1, false);
+    }
+    return (int)hipGetLastError();
+  }
+#undef FWD_Q1
 #define FWD_V(NK, NW, WP, DR)                                                                                          \
     hipLaunchKernelGGL((attn_fwd_kernel<NK, NW, WP, DR>), grid, dim3(NW * 64), attn_lds_bytes<NK>(), st,                \
                        reinterpret_cast<const h16*>(a->qkv), a->keymask, reinterpret_cast<h16*>(a->ctx), a->lse, a->S, \
@@ -1073,16 +1105,17 @@ extern "C" int vault_attention_bwd(const vault_attn_args* a, void* stream) {
   if (a->qkv_hm != 0 && (a->qkv_hm < a->B * a->S || a->S > 192)) return VAULT_EINVAL;
   // bias partials: the single-pass kernels; the query third alone, or (S <= 64: LDS) all three
   if (a->bias_partials != nullptr && vault_attention_bwd_partials(a) == 0) return VAULT_EINVAL;
+  if (a->q_rows != 0 && (a->q_rows != 1 || a->S > 192)) return VAULT_EINVAL;   // one live query per item: the single-pass kernels
   const int cs_bytes = a->bias_partials ? a->bias_thirds * a->H * 4 : 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const AttnDrop dr{a->drop_thresh, a->drop_seed, a->drop_stream, a->drop_scale};
   dim3 grid(a->heads, a->B), block(256);
   const float scale = 0.125f;
   const bool drop = a->drop_thresh != 0u;
-#define ONE_V(DR)                                                                                                             \
+#define ONE_V(DR, Q)                                                                                                          \
     {                                                                                                                         \
       /* 152 KiB of LDS (+ 4 KiB of bias partials): one workgroup per CU, persistent; ATTN_BWD_KT key tiles per wave */ \
-      auto kern = attn_bwd_one_kernel<6, 12 / ATTN_BWD_KT, DR, (ATTN_BWD_KT == 1 ? 1 : (ATTN_BWD_KT == 2 ? 2 : 1)), ATTN_BWD_KT>;   \
+      auto kern = attn_bwd_one_kernel<6, 12 / ATTN_BWD_KT, DR, (ATTN_BWD_KT == 1 ? 1 : (ATTN_BWD_KT == 2 ? 2 : 1)), ATTN_BWD_KT, Q>;   \
       static bool attr_done_dev[64] = {}; int attr_dev = 0; (void)hipGetDevice(&attr_dev); bool& attr_done = attr_done_dev[(attr_dev >= 0 && attr_dev < 64) ? attr_dev : 0];                                                                                          \
       if (!attr_done) {                                                                                                       \
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,   \
@@ -1100,6 +1133,15 @@ extern "C" int vault_attention_bwd(const vault_attn_args* a, void* stream) {
     // three workgroups per CU (35 KiB of LDS, <= 168 registers), persistent over the (batch, head) items
     const int items = a->B * a->heads;
     const int grid = items < 768 ? items : 768;
+#define ONE_S(DR)                                                                                                                 \
+    hipLaunchKernelGGL((attn_bwd_one_kernel<2, 4, DR, 3, 1, true>), dim3(grid), dim3(256), attn_one_lds_bytes<2>() + cs_bytes, st, \
+                       reinterpret_cast<const h16*>(a->qkv), a->keymask, reinterpret_cast<const h16*>(a->ctx),                  \
+                       reinterpret_cast<const h16*>(a->dctx), a->lse, reinterpret_cast<h16*>(a->dqkv), a->S, a->H,              \
+                       a->heads, items, scale, dr, a->qkv_hm, a->bias_partials, a->bias_thirds)
+    if (a->q_rows == 1) {
+      if (drop) ONE_S(true); else ONE_S(false);
+    } else
+#undef ONE_S
     if (drop) hipLaunchKernelGGL((attn_bwd_one_kernel<2, 4, true, 3>), dim3(grid), dim3(256), attn_one_lds_bytes<2>() + cs_bytes, st,
                                  reinterpret_cast<const h16*>(a->qkv), a->keymask, reinterpret_cast<const h16*>(a->ctx),
                                  reinterpret_cast<const h16*>(a->dctx), a->lse, reinterpret_cast<h16*>(a->dqkv), a->S, a->H,
@@ -1110,7 +1152,9 @@ extern "C" int vault_attention_bwd(const vault_attn_args* a, void* stream) {
                             a->heads, items, scale, dr, a->qkv_hm, a->bias_partials, a->bias_thirds);
   } else if (a->S <= 192) {
     const int items = a->B * a->heads;
-    if (drop) ONE_V(true) else ONE_V(false)
+    if (a->q_rows == 1) {
+      if (drop) ONE_V(true, true) else ONE_V(false, true)
+    } else if (drop) ONE_V(true, false) else ONE_V(false, false)
   } else if (a->S <= 288) {
     auto kern = attn_bwd_kernel<9, ATTN_L9_BWD_W, ATTN_L9_BWD_WPE>;
     static bool attr_done_dev[64] = {}; int attr_dev = 0; (void)hipGetDevice(&attr_dev); bool& attr_done = attr_done_dev[(attr_dev >= 0 && attr_dev < 64) ? attr_dev : 0];

@@ -386,6 +386,16 @@ extern "C" int vault_scale_f32(float* x, float a, long long n, void* stream) {
 // through TomViltForTMSC, ref: vault/models/tomvilt/model.py:281-287).
 // fwd: out[map(r)] = src[r] + vec   ; map(r) = (r / rpg) * gstride + goff + r % rpg  (rows of the fused sequence)
 // bwd: dsrc[r] = dx[map(r)] ; dvec += column sums of those rows
+__global__ __launch_bounds__(256) void rows_scatter_h16_kernel(const h16* __restrict__ src, h16* __restrict__ out, int rows, int H,
+                                                               int rpg, int gstride, int goff) {
+  const int h8 = H >> 3;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < (long long)rows * h8; i += (long long)gridDim.x * 256) {
+    const int r = (int)(i / h8), c = (int)(i - (long long)r * h8) * 8;
+    const size_t orow = (size_t)(r / rpg) * gstride + goff + (r % rpg);
+    *reinterpret_cast<u32x4*>(out + orow * H + c) = *reinterpret_cast<const u32x4*>(src + (size_t)r * H + c);
+  }
+}
+
 __global__ __launch_bounds__(256) void rows_add_kernel(const float* __restrict__ src, const float* __restrict__ vec,
                                                        float* __restrict__ out, int rows, int H, int rpg, int gstride, int goff) {
   const int h4 = H >> 2;
@@ -417,6 +427,15 @@ __global__ __launch_bounds__(256) void rows_gather_bwd_kernel(const float* __res
       for (int e = 0; e < 4; ++e) atomicAdd(dvec + cg * 4 + e, acc[e]);
     }
   }
+}
+
+extern "C" int vault_rows_scatter_bf16(const void* src, void* out, int rows, int H, int rpg, int gstride, int goff, void* stream) {
+  if (!src || !out || rows <= 0 || H <= 0 || (H & 7) || rpg <= 0) return VAULT_EINVAL;
+  const long long n = (long long)rows * (H >> 3);
+  hipLaunchKernelGGL(rows_scatter_h16_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 8192)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const h16*>(src), reinterpret_cast<h16*>(out), rows, H,
+                     rpg, gstride, goff);
+  return (int)hipGetLastError();
 }
 
 extern "C" int vault_rows_add_f32(const float* src, const float* vec, float* out, int rows, int H, int rpg, int gstride,

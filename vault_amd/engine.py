@@ -55,6 +55,13 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
     WGRAD_STREAM_MAX_ROWS = 16384  # deferred weight gradients run on a second stream up to this many ViLT token rows (B <= 88)
     WGRAD_BATCH_MAX_ROWS = 131072  # the ViLT layers take the same route up to this many (padded) token rows (B <= 708:
                                    # 22 GB of per-layer dY operands at that size; 7.9 GB at B = 256)
+    # The last ViLT layer computes only what the pooler reads when nothing else reads its output (need_hidden=False): behind its
+    # K / V projection every kernel runs on the B CLS rows - attention with one live query per item (vault_attn_args.q_rows),
+    # attention-out, LayerNorm 2 and the FFN at M = 256-padded B, and their backward on the same rows (see _plan_prune,
+    # _vilt_last_layer_pruned, backward._vilt_last_layer_bwd_pruned).  VAULT_PRUNE_LAST_LAYER=0 in the environment of the
+    # constructor switches it off (A/B runs).
+    PRUNE_LAST_LAYER = True
+    PRUNE_MIN_ROWS = 16384         # ... from this many (padded) token rows (HEAD_MAJOR_MIN_ROWS: small shapes keep one path)
 
     def __init__(self, spec: VaultSpec, device="cuda:0", state=None, seed: int = 0, freeze_lm: bool = False,
                  with_grads: bool = True, classifier_dropout: float = 0.1, fp8_forward: bool = False,
@@ -129,6 +136,8 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
         # each 16-bit tensor of the workspace - {"forward" | "backward": {tensor name: {"saturated", "nonfinite", "subnormal",
         # "zero", "n"}}} (vault_h16_census: elements at the largest finite magnitude = what a saturating conversion leaves)
         self.census_on = os.environ.get("VAULT_H16_CENSUS") == "1"
+        if os.environ.get("VAULT_PRUNE_LAST_LAYER") == "0":
+            self.PRUNE_LAST_LAYER = False
         self.census: Dict[str, Dict[str, dict]] = {}
 
     def _prof_begin(self, site: str, stream=None):
@@ -149,7 +158,7 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
         import re
         skip_u = ws.get("gelu8_active") is not None       # (the ViLT `u` buffers then hold the 8-bit tile-native gelu' image)
         names = [k for k, t in ws.items() if isinstance(k, str) and isinstance(t, torch.Tensor) and t.dtype == self.hdt
-                 and not k.endswith("_all") and not (skip_u and re.fullmatch(r"u\d*", k))]
+                 and not k.endswith("_all") and not (skip_u and re.fullmatch(r"(pl_)?u\d*", k))]
         seen, todo = set(), []
         for k in sorted(names):
             key = (ws[k].data_ptr(), ws[k].numel())
@@ -260,8 +269,19 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
         have stored (a strided device copy, no arithmetic) - what the bf16 backward reads in a precise-forward training step."""
         ops.pycall(lambda: plain.copy_(split3[:, :K]))
 
+    def _cfg_like(self, key, plan, M, like):
+        """Kernel configuration of a compact GEMM of the pruned last layer (``M`` rows): the one the library chooses for the
+        same call over the ``like`` rows of the full-size layer, if it accepts ``M`` rows - a row's arithmetic does not depend
+        on the other rows of its tile, so the compact result equals the full-size call's rows bit for bit - else the library's
+        own choice (-1).  ``plan(rows, cfg)``: vault_gemm_plan of the call.  Asked once per engine and call site."""
+        key = ("cfg_like",) + key + (M, like, ops.GEMM_SCHED)
+        if key not in self._ws:
+            c = plan(like, -1)
+            self._ws[key] = c if (c >= 0 and plan(M, c) == c) else -1
+        return self._ws[key]
+
     def _linear(self, a_bf16, wname, out, M, N, K, epi, m_valid, bias=None, precise=False, ldo=None, prequant=False,
-                emit_q=False, **kw):
+                emit_q=False, like=None, **kw):
         """out = epilogue(A . W^T).  ``precise``: A is a [M, 3K] = [hi | lo | hi] split-bf16 operand and the
         weight its [N, 3K] = [hi | hi | lo] counterpart: the same kernel over a 3x longer contraction.
         fp8-forward mode: ``prequant`` - the MXFP8 image of A already lies in the (M, K) scratch (False for a Linear whose
@@ -291,9 +311,15 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
             ops.gemm_mxfp8(aq, asc, wq, wsc, out, M, N, K, N, epi, m_valid=m_valid, bias=bias, **kw)
             return emit_q
         else:
-            if epi == ops.EPI_F32_RES and K >= 1536:
+            w = P.wb(wname, n_elems=N * K, shape=(N, K))
+            if like is not None and "cfg" not in kw:      # (compact call of the pruned last layer: the full-size call's kernel)
+                kwl = dict(kw, splitk_ws=self._sk_ws()) if (epi == ops.EPI_F32_RES and K >= 1536) else kw
+                kw["cfg"] = self._cfg_like(("lin", wname, epi), lambda m, c: ops.gemm(
+                    a_bf16, w, out, m, N, K, K, K, N if ldo is None else ldo, 0, 0, epi, m_valid=m, bias=bias, cfg=c,
+                    plan_only=True, **(kwl if c < 0 else kw)), M, like)
+            elif epi == ops.EPI_F32_RES and K >= 1536:
                 kw.setdefault("splitk_ws", self._sk_ws())
-            ops.gemm(a_bf16, P.wb(wname, n_elems=N * K, shape=(N, K)), out, M, N, K, K, K, N if ldo is None else ldo,
+            ops.gemm(a_bf16, w, out, M, N, K, K, K, N if ldo is None else ldo,
                      0, 0, epi, m_valid=m_valid, bias=bias, **kw)
 
     def _fp8_kernel_ok(self, M, N, K, epi, out, bias, kw) -> bool:
@@ -309,18 +335,26 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
                                            plan_only=True) in (5, 6)
         return self._ws[key]
 
-    def _dgrad(self, dy_bf16, wname, out, M, Kin, Nout, epi, m_valid, **kw):
-        # dX[M,Kin] = dY[M,Nout] . W[Nout,Kin]
+    def _dgrad(self, dy_bf16, wname, out, M, Kin, Nout, epi, m_valid, like=None, **kw):
+        # dX[M,Kin] = dY[M,Nout] . W[Nout,Kin]      (``like``: compact call of the pruned last layer, _cfg_like)
         P = self.params
         wt = P.pbT.get(wname)
         if wt is not None and M % 256 == 0:
             # forward-form operands on the transposed shadow W^T [Kin][Nout]: the register-direct GEMM
+            if like is not None and "cfg" not in kw:
+                kw["cfg"] = self._cfg_like(("dgrad", wname, epi), lambda m, c: ops.gemm(
+                    dy_bf16, wt, out, m, Kin, Nout, Nout, Nout, Kin, 0, 0, epi, m_valid=m, cfg=c, plan_only=True, **kw), M, like)
             ops.gemm(dy_bf16, wt, out, M, Kin, Nout, Nout, Nout, Kin, 0, 0, epi, m_valid=m_valid, **kw)
             return
-        if epi == ops.EPI_BF16 and Nout >= 1536:
+        w = P.wb(wname, n_elems=Nout * Kin, shape=(Nout, Kin))
+        if like is not None and "cfg" not in kw and M % 256 == 0:
+            kwl = dict(kw, splitk_ws=self._sk_ws()) if (epi == ops.EPI_BF16 and Nout >= 1536) else kw
+            kw["cfg"] = self._cfg_like(("dgrad", wname, epi), lambda m, c: ops.gemm(
+                dy_bf16, w, out, m, Kin, Nout, Nout, Kin, Kin, 0, 1, epi, m_valid=m, cfg=c, plan_only=True,
+                **(kwl if c < 0 else kw)), M, like)
+        elif epi == ops.EPI_BF16 and Nout >= 1536:
             kw.setdefault("splitk_ws", self._sk_ws())
-        ops.gemm(dy_bf16, P.wb(wname, n_elems=Nout * Kin, shape=(Nout, Kin)), out, M, Kin, Nout, Nout, Kin, Kin, 0, 1,
-                 epi, m_valid=m_valid, **kw)
+        ops.gemm(dy_bf16, w, out, M, Kin, Nout, Nout, Kin, Kin, 0, 1, epi, m_valid=m_valid, **kw)
 
 
     FFN_OUT_FP8 = False            # fp8-forward mode: FFN-out on MXFP8 operands too (see _fp8_refresh_weights: measured, slower)
@@ -519,7 +553,8 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
         only a training step keeps the plain 16-bit form, in buffer ``name``: what the bf16 backward reads."""
         return y16 if not pr else (self._buf(ws, name, shape, self.hdt) if ws["train"] else None)
 
-    def _ffn_forward(self, ws, a16, ln, pre, sfx, rows, rows_pad, res, out, u, act, pr, prequant, drop=NO_DROP, g8=None):
+    def _ffn_forward(self, ws, a16, ln, pre, sfx, rows, rows_pad, res, out, u, act, pr, prequant, drop=NO_DROP, g8=None,
+                     like=None):
         """act = gelu(a16 . Wi^T + bi) with gelu' into ``u`` (training), out = res + dropout(act . Wf^T + bf).  ``pre`` + name + ``sfx``:
         workspace names; ``g8``: _plan_gelu8.  Returns FFN-out's `prequant`: whether FFN-in's epilogue wrote its MXFP8 image."""
         P, H, FF, bf, W3, pt = self.params, ws["H"], ws["FF"], self.hdt, (3 if pr else 1), pr and ws["train"]
@@ -528,7 +563,7 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
         #  whose first third is written)
         u_out = self._buf(ws, f"{pre}u{sfx}_3", (rows_pad, W3 * FF), bf) if (pt and u is not None) else u
         actq = self._linear(a16, ln.iw, act, rows_pad, FF, H, ops.EPI_BF16_GELU, rows, bias=P.w(ln.ib), out2=u_out, precise=pr,
-                            split3=pr, ldo=W3 * FF, prequant=prequant, emit_q=self.FFN_OUT_FP8,
+                            split3=pr, ldo=W3 * FF, prequant=prequant, emit_q=self.FFN_OUT_FP8, like=like,
                             **(dict(cfg=g8, aux_u8=True) if g8 is not None else {}))
         if pt:
             self._keep_hi(act, self._buf(ws, f"{pre}act{sfx}", (rows_pad, FF), bf), FF)
@@ -536,7 +571,7 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
                 self._keep_hi(u_out, u, FF)
         ops.pycall(lambda: self._prof_end("ffn1", 2.0 * rows * FF * H * W3))
         self._linear(act, ln.fw, out, rows_pad, H, FF, ops.EPI_F32_RES, rows, bias=P.w(ln.fb), res=res, drop=drop, precise=pr,
-                     prequant=bool(actq))
+                     prequant=bool(actq), like=like)
         return bool(actq)
 
     def _lm_forward(self, ws, pr, buf, bf):
@@ -657,6 +692,51 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
             ops.image_pos_sel_fwd(x[0], P.w("embeddings.position_embeddings"), ws["sel"], ws["hw"], B, NP, S, T, H,
                                   ws["gw"], v.image_size // v.patch_size)
 
+    def _plan_prune(self, ws, need_hidden, pr) -> bool:
+        """Whether this forward computes the last ViLT layer on the CLS rows only (PRUNE_LAST_LAYER): nothing but the pooler
+        reads the layer's output, the per-kernel path is in use at a batch where it pays, and the attention kernels have their
+        one-query form for the shape (vault_attn_args.q_rows: the resident kernels, S <= 192, plain 16-bit ctx)."""
+        return bool(self.PRUNE_LAST_LAYER and self.spec.add_pooling_layer and not need_hidden and not self.keep_layer_outputs
+                    and not pr and not self.fp8_forward and not self._use_stage(ws["Mp"], pr)
+                    and ws["Mp"] >= self.PRUNE_MIN_ROWS and ws["S"] <= 192 and len(self.vl) > 0)
+
+    def _vilt_last_layer_pruned(self, ws, x, i, km, train, buf, bf):
+        """The last ViLT layer for the pooler alone.  LayerNorm 1 and the QKV projection run over all rows (every key and value
+        is needed); attention computes query row 0 of every item into a compact [Bp, H] ctx; attention-out (on the CLS rows of
+        the residual stream, gathered), LayerNorm 2 and the FFN run on those Bp rows, on the kernels of the full-size calls
+        (_cfg_like): the logits equal the unpruned forward's bit for bit.  Buffers ``pl_*``; x[i + 1] is not written."""
+        P, v, ln = self.params, self.spec.vilt, self.vl[i]
+        B, S, M, Mp, H, FF, heads = (ws[k] for k in ("B", "S", "M", "Mp", "H", "FF", "heads"))
+        Bp = ws["Bp"] = _pad(B)
+        sfx, like = (f"{i}" if train else ""), Mp
+        n1, qkv, lse = buf(f"n1{sfx}", (Mp, H), bf), buf(f"qkv{sfx}", (Mp, 3 * H), bf), buf(f"lse{sfx}", (B, heads, S))
+        ws["vilt_stage"] = False
+        ops.layernorm_fwd(x[i], P.w(ln.ln1w), P.w(ln.ln1b), v.layer_norm_eps, M, H, y_bf16=n1,
+                          mean=buf(f"m1{sfx}", (Mp,)), rstd=buf(f"r1{sfx}", (Mp,)))
+        vhm = self._plan_head_major(ws, "qkv_hm", n1, ln.qw, Mp, M, S, False, train)
+        self._linear(n1, ln.qw, qkv, Mp, 3 * H, H, ops.EPI_BF16, M, bias=P.w(ln.qb, n_elems=3 * H, shape=(3 * H,)),
+                     **(dict(out_hm=vhm) if vhm else {}))
+        ctx, xres, xm = buf("pl_ctx", (Bp, H), bf), buf("pl_xres", (Bp, H)), buf("pl_xm", (Bp, H))
+        ops.attention_fwd(qkv, km, ctx, lse, B, S, H, heads, qkv_hm=vhm, q_rows=1)
+        ops.rows_gather_bwd(x[i], xres, None, B, H, 1, S, 0)          # xres[b] = x[i][b S]: the CLS rows of the residual stream
+        self._linear(ctx, ln.ow, xm, Bp, H, H, ops.EPI_F32_RES, B, bias=P.w(ln.ob), res=xres, like=like)
+        n2 = buf("pl_n2", (Bp, H), bf)
+        ops.layernorm_fwd(xm, P.w(ln.ln2w), P.w(ln.ln2b), v.layer_norm_eps, B, H, y_bf16=n2,
+                          mean=buf("pl_m2", (Bp,)), rstd=buf("pl_r2", (Bp,)))
+        u, act = (buf("pl_u", (Bp, FF), bf) if train else None), buf("pl_act", (Bp, FF), bf)
+        # the 8-bit gelu' image on the full-size layers' kernel, if that kernel serves both compact calls of the pair
+        g8 = self._plan_gelu8(ws, n2, act, u, ln, Mp, M)
+        if g8 is not None and ws.get("pl_gelu8_of") != (g8, ops.GEMM_SCHED):
+            wt = P.pbT.get(ln.fw)
+            c1 = ops.gemm(n2, P.wb(ln.iw, n_elems=FF * H, shape=(FF, H)), act, Bp, FF, H, H, H, FF, 0, 0, ops.EPI_BF16_GELU,
+                          m_valid=B, bias=P.w(ln.ib), out2=u, aux_u8=True, cfg=g8, plan_only=True)
+            c2 = ops.gemm(n2, wt, act, Bp, FF, H, H, H, FF, 0, 0, ops.EPI_BF16_DGELU, m_valid=B, aux=u, colsum=P.gr(ln.ib),
+                          aux_u8=True, cfg=g8, plan_only=True)
+            ws["pl_gelu8_of"], ws["pl_gelu8_ok"] = (g8, ops.GEMM_SCHED), (c1 == g8 and c2 == g8)
+        g8 = g8 if (g8 is not None and ws["pl_gelu8_ok"]) else None
+        ws["pl_gelu8"] = g8         # what THIS forward stored in `pl_u`
+        self._ffn_forward(ws, n2, ln, "pl_", "", B, Bp, xm, buf("pl_xout", (Bp, H)), u, act, False, None, g8=g8, like=like)
+
     def _forward_encoder(self, ws, x, need_hidden, loss_scale, pr, W3, labels, km, train, buf, bf):
         spec, P = self.spec, self.params
         v = spec.vilt
@@ -669,8 +749,12 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
             # the ViLT layers' weight gradients are deferred and batched like the LM's
             for base, width in (("n1", H), ("ctx", H), ("n2", H), ("act", FF)):
                 self._stack(ws, base, nv, (Mp, width), bf)
+        prune = ws["pruned_last"] = self._plan_prune(ws, need_hidden, pr)
         ops.pycall(lambda: self._prof_begin("vilt_fwd"))
         for i, ln in enumerate(self.vl):
+            if prune and i == nv - 1:
+                self._vilt_last_layer_pruned(ws, x, i, km, train, buf, bf)
+                continue
             sfx = f"{i}" if train else ""
             p3 = "_3" if pr else ""
             n1 = buf(f"n1{sfx}{p3}", (Mp, W3 * H), bf); qkv = buf(f"qkv{sfx}", (Mp, 3 * H), bf)
@@ -721,9 +805,10 @@ class VaultEngine(StagingMixin, HeadsMixin, BackwardMixin):
             Bp = _pad(B)
             ws["Bp"] = Bp
             h0b = buf("h0b_3" if pr else "h0b", (Bp, W3 * H), bf)
-            ops.layernorm_fwd(xl, lw, lb, v.layer_norm_eps, B, H, y_bf16=self._ln_y16(ws, pr, h0b, "h0b", (Bp, H)),
-                              y_split3=h0b if pr else None, xmap=(1, S, 0), mean=buf("f_mean", (Bp,)),
-                              rstd=buf("f_rstd", (Bp,)))
+            # (pruned last layer: its output is compact, one row per sample)
+            ops.layernorm_fwd(ws["pl_xout"] if prune else xl, lw, lb, v.layer_norm_eps, B, H,
+                              y_bf16=self._ln_y16(ws, pr, h0b, "h0b", (Bp, H)), y_split3=h0b if pr else None,
+                              xmap=(0, 0, 0) if prune else (1, S, 0), mean=buf("f_mean", (Bp,)), rstd=buf("f_rstd", (Bp,)))
             pre = buf("pool_pre", (Bp, H))
             self._linear(h0b, "pooler.dense.weight", pre, Bp, H, H, ops.EPI_F32_RES, B, bias=P.w("pooler.dense.bias"),
                          precise=pr)

@@ -43,7 +43,7 @@ class AttnArgs(C.Structure):
                 ("B", C.c_int), ("S", C.c_int), ("H", C.c_int), ("heads", C.c_int),
                 ("drop_thresh", C.c_uint32), ("drop_seed", C.c_uint32), ("drop_stream", C.c_uint32),
                 ("drop_scale", C.c_float), ("ctx_split3", C.c_void_p), ("qkv_hm", C.c_int),
-                ("bias_partials", C.c_void_p), ("bias_thirds", C.c_int)]
+                ("bias_partials", C.c_void_p), ("bias_thirds", C.c_int), ("q_rows", C.c_int)]
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -328,8 +328,10 @@ def colsum(x_bf16, ld, rows, N, out):
     _invoke("vault_colsum", C.c_void_p(_p(x_bf16)), C.c_int(ld), C.c_int(rows), C.c_int(N), C.c_void_p(_p(out)), _stream())
 
 
-def _attn_args(qkv, keymask, ctx, lse, B, S, H, heads, dctx=None, dqkv=None, drop: Drop = NO_DROP, ctx_split3=None, qkv_hm=0):
+def _attn_args(qkv, keymask, ctx, lse, B, S, H, heads, dctx=None, dqkv=None, drop: Drop = NO_DROP, ctx_split3=None, qkv_hm=0,
+               q_rows=0):
     a = AttnArgs()
+    a.q_rows = int(q_rows)      # 1: only query row 0 of every item is live, ctx / dctx are compact [B][H] (vault_attn_args.q_rows)
     a.qkv_hm = int(qkv_hm)      # > 0: qkv / dqkv in the head-major layout [3][heads][qkv_hm rows][64] (vault_attn_args.qkv_hm)
     a.ctx_split3 = _h(ctx_split3)
     a.qkv, a.keymask, a.ctx, a.lse, a.dctx, a.dqkv = _h(qkv), _p(keymask), _h(ctx), _p(lse), _h(dctx), _h(dqkv)
@@ -338,16 +340,16 @@ def _attn_args(qkv, keymask, ctx, lse, B, S, H, heads, dctx=None, dqkv=None, dro
     return a
 
 
-def attention_fwd(qkv, keymask, ctx, lse, B, S, H, heads, drop: Drop = NO_DROP, ctx_split3=None, qkv_hm=0):
-    a = _attn_args(qkv, keymask, ctx, lse, B, S, H, heads, drop=drop, ctx_split3=ctx_split3, qkv_hm=qkv_hm)
+def attention_fwd(qkv, keymask, ctx, lse, B, S, H, heads, drop: Drop = NO_DROP, ctx_split3=None, qkv_hm=0, q_rows=0):
+    a = _attn_args(qkv, keymask, ctx, lse, B, S, H, heads, drop=drop, ctx_split3=ctx_split3, qkv_hm=qkv_hm, q_rows=q_rows)
     _invoke("vault_attention_fwd", C.byref(a), _stream(), struct=a, drop=drop)
 
 
 def attention_bwd(qkv, keymask, ctx, lse, dctx, dqkv, B, S, H, heads, drop: Drop = NO_DROP, qkv_hm=0, bias_partials=None,
-                  bias_thirds=1):
+                  bias_thirds=1, q_rows=0):
     """``bias_partials``: f32 [attention_bwd_partials(...), bias_thirds * H] - the launch's workgroups leave the column sums of
     dq (| dk | dv) over their items there (the QKV bias gradient without a pass over dqkv; colsum_partials adds the rows)."""
-    a = _attn_args(qkv, keymask, ctx, lse, B, S, H, heads, dctx, dqkv, drop, qkv_hm=qkv_hm)
+    a = _attn_args(qkv, keymask, ctx, lse, B, S, H, heads, dctx, dqkv, drop, qkv_hm=qkv_hm, q_rows=q_rows)
     a.bias_partials, a.bias_thirds = _p(bias_partials), (int(bias_thirds) if bias_partials is not None else 0)
     _invoke("vault_attention_bwd", C.byref(a), _stream(), struct=a, drop=drop)
 
@@ -644,6 +646,12 @@ def transpose_bf16(src, dst, rows, cols, batch=1, stride_src=0, stride_dst=0):
 def rows_add(src, vec, out, rows, H, rpg, gstride, goff):
     _invoke("vault_rows_add_f32", C.c_void_p(_p(src)), C.c_void_p(_p(vec)), C.c_void_p(_p(out)), C.c_int(rows), C.c_int(H),
             C.c_int(rpg), C.c_int(gstride), C.c_int(goff), _stream())
+
+
+def rows_scatter_h16(src, out, rows, H, rpg, gstride, goff):
+    """out[(r // rpg) * gstride + goff + r % rpg] = src[r] over 16-bit rows (vault_rows_scatter_bf16)."""
+    _invoke("vault_rows_scatter_bf16", C.c_void_p(_h(src)), C.c_void_p(_h(out)), C.c_int(rows), C.c_int(H), C.c_int(rpg),
+            C.c_int(gstride), C.c_int(goff), _stream())
 
 
 def rows_gather_bwd(dx, dsrc, dvec, rows, H, rpg, gstride, goff):
